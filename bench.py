@@ -11,9 +11,14 @@ inputs resident in HBM before the timed region starts:
                         on one stream; the path KoopmanMPCStrategy.rebalance_batch runs)
     [N > 1] dist.gather(W0 -> rank 0)              (the one RCCL collective)
 
-After the timed region the same step runs once more per timed step as two C-ABI calls
-(kmpc_rollout, kmpc_solve) so that HIP events bracket the solve alone (the dominant kernels) for
-the roofline figure; the line carries both (timed_path, kernels.two_call_ms_per_step).
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit,
+ms_per_step, dtype, config, the timed step's solver statistics). --dump-outputs DIR also saves what
+the last timed step returned (dump_outputs). Everything else runs only with --full, after the
+timed region: the same step once more per timed step as two C-ABI calls (kmpc_rollout, kmpc_solve)
+so that HIP events bracket the solve alone (the dominant kernels) for the roofline figure (the line
+then carries timed_path and kernels.two_call_ms_per_step), the rollout's parity against float64,
+the secondary configurations and the CPU baselines with their parity spot check (--headline-only
+and --cpu-seconds trim those two).
 
 Workload. N = 1: BASELINE configs[2], 65536 windows, N = 100 assets, latent
 L = 256, H = 10, obs = N * 20 = 2000, the finance_sparse GenericKM layout (encoder
@@ -25,7 +30,8 @@ synthetic and seeded; every window's (obs, w_prev) is a function of its index in
 (window_inputs), so the N = 1 batch is the first 65536 windows of the C4 stream and a window's
 inputs (and result) do not depend on the GPU count.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]; for N > 1 launch under torch.distributed.run.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N > 1
+launch under torch.distributed.run.
 """
 from __future__ import annotations
 
@@ -111,8 +117,13 @@ def parse():
     p.add_argument("--horizon", type=int, default=10)
     p.add_argument("--emb", type=int, default=20)
     p.add_argument("--hidden", type=int, default=1024)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the kernel split (roofline, compute utilisation), the "
+                        "rollout parity check, the secondary configurations and the CPU baselines")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 saves what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     p.add_argument("--cpu-seconds", type=float, default=20.0,
-                   help="approximate CPU-baseline budget (0 disables the cpu_baseline leg)")
+                   help="with --full: approximate CPU-baseline budget (0 disables the cpu_baseline leg)")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                    help="process-group backend for N > 1 (nccl = RCCL over xGMI, the default; gloo moves "
                         "the W0 gather and the timing collectives through host copies)")
@@ -120,7 +131,7 @@ def parse():
                    help="every rank uses cuda:0 (a readiness check of the sharded path on a one-GPU box, "
                         "with --backend gloo: not a scaling figure)")
     p.add_argument("--headline-only", action="store_true",
-                   help="skip the secondary configurations and the CPU baselines")
+                   help="with --full: skip the secondary configurations and the CPU baselines")
     p.add_argument("--dump-w0", default="",
                    help="rank 0 saves the (gathered) W0 of the last timed step to this .npy file")
     return p.parse_args()
@@ -648,6 +659,31 @@ def rollout_parity(model, sd, x, mean_d, std_d, H, N, n=512) -> dict:
             "f32_input_mfma_max_rel_err": float(np.abs(y1 - ref).max() / scale)}
 
 
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs writes at most this much array data (under 64 MB with headers)
+
+
+def dump_outputs(out_dir: str, W0, status=None, value=None, iters=None) -> None:
+    """--dump-outputs: what DeviceKoopman.window returned in the last timed step, one .npy per array:
+    W0 [G, N] float64 (the gathered W0 at N > 1) and, at N = 1, value [G] float64 and status, iters
+    [G] as float32 (small integers, exact). The inputs are seeded, so two builds run with the same
+    arguments can be compared file by file. If the rows would exceed DUMP_MAX_BYTES, the same
+    sorted sample of rows, drawn without replacement from a generator seeded 0, is kept of every
+    array, and rows.npy (float64) holds their indices; otherwise every row is written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"W0": (W0, np.float64)}
+    if status is not None:
+        arrays.update({"value": (value, np.float64), "status": (status, np.float32), "iters": (iters, np.float32)})
+    G = int(W0.shape[0])
+    row_bytes = 8 + sum(np.dtype(dt).itemsize * int(np.prod(t.shape[1:])) for t, dt in arrays.values())
+    keep = None
+    if G * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(G, DUMP_MAX_BYTES // row_bytes, replace=False))
+        np.save(os.path.join(out_dir, "rows.npy"), keep.astype(np.float64))
+    for name, (t, dt) in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray((a if keep is None else a[keep]).astype(dt)))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -702,27 +738,62 @@ def main():
         prov["share_device"] = bool(args.share_device)
     if args.dump_w0 and rank == 0:
         np.save(args.dump_w0, Wg.cpu().numpy())
-
-    # kernel split, after the timed region: the same step as two C-ABI calls (kmpc_rollout, then
-    # kmpc_solve), each bracketed by HIP events on the launch stream — the solve's launch time is
-    # the roofline's; their sum is checked against the fused step's time (two_call_ms_per_step)
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
-    for e in ev:
-        e[0].record()
-        y = model.rollout(x, mean_d, std_d, H, N)
-        e[1].record()
-        W0s, _, _ = solve_mpc_log_utility_batched(wp, y, cfg)
-        e[2].record()
-    torch.cuda.synchronize()
-    if not torch.equal(W0s, W0):
-        sys.exit("bench: the fused window and rollout-then-solve disagree")
-    roll_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
-    solve_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Wg, *((st, val, its) if world == 1 else (None, None, None)))
     st_np = st.cpu().numpy()
     n_opt = int((st_np <= 1).sum())
+    c4 = world > 1
 
     if rank == 0:
         value = G * args.steps / elapsed
+        line = {
+            "metric": METRIC, "value": value, "unit": "windows/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong" if c4 else "weak", "vs_baseline": None,
+            "dtype": "f32 rollout (fp32 GEMMs as three exact bf16 planes); mixed f32->f64 IPM solve "
+                     "(float32 phase to mu 3e-5, float64 finish: stopping rule, status and W in float64)",
+            "data": "synthetic (seeded N(0,1) standardized embeddings, Dirichlet w_prev, random-init finance_sparse weights)",
+            "config": {"workload": (f"C4 (BASELINE configs[3]): {G} windows/step over {world} GPUs" if c4 else
+                                    f"C3 (BASELINE configs[2]): {G} windows/GPU") +
+                                   f", {N} assets, latent {L}, H={H}, obs {obs}, GenericKM enc "
+                                   f"[{args.hidden},{args.hidden}], L1-turnover MPC c=1e-3 tau=0.2 no-short",
+                       "windows_per_gpu": B, "global_windows_per_step": G,
+                       "parallelism": ((f"windows sharded over {world} ranks sharing cuda:0 (readiness check, not "
+                                        f"a scaling figure), {args.backend} gather of W0 to rank 0")
+                                       if args.share_device and c4 else
+                                       f"windows sharded over {world} GPUs (contiguous blocks of one global "
+                                       f"stream), {'RCCL' if args.backend == 'nccl' else 'gloo'} gather of W0 to rank 0"
+                                       if c4 else "1 GPU, no collective")}
+                      | ({"dist": prov} if prov else {}),
+            # SURVEY.md §8(d)'s whole-path bound: compulsory bytes per window = obs (f32 N d) +
+            # w_prev + w0 (f32 as there), weights amortized: windows/s x bytes / 8 TB/s
+            "path_hbm_roofline": {"bound": "hbm", "bytes_per_window": 4 * obs + 8 * N,
+                                  "achieved": value / world * (4 * obs + 8 * N) / 1e9, "peak": HBM_PEAK / 1e9,
+                                  "unit": "GB/s", "frac": value / world * (4 * obs + 8 * N) / HBM_PEAK,
+                                  "ceiling_windows_per_s_per_gpu": HBM_PEAK / (4 * obs + 8 * N)},
+            "timed_path": "kmpc_window via DeviceKoopman.window (the KoopmanMPCStrategy.rebalance_batch path)",
+            "solver": {"optimal_or_inaccurate": n_opt, "windows": B,
+                       "mean_ipm_iterations": float(its.float().mean().item())},
+        }
+
+    if args.full:
+        # kernel split, after the timed region: the same step as two C-ABI calls (kmpc_rollout, then
+        # kmpc_solve), each bracketed by HIP events on the launch stream — the solve's launch time is
+        # the roofline's; their sum is checked against the fused step's time (two_call_ms_per_step)
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+        for e in ev:
+            e[0].record()
+            y = model.rollout(x, mean_d, std_d, H, N)
+            e[1].record()
+            W0s, _, _ = solve_mpc_log_utility_batched(wp, y, cfg)
+            e[2].record()
+        torch.cuda.synchronize()
+        if not torch.equal(W0s, W0):
+            sys.exit("bench: the fused window and rollout-then-solve disagree")
+        roll_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+        solve_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+
+    if rank == 0 and args.full:
         # roofline of the dominant kernel (the solve), SURVEY §8(d): ALGORITHMIC HBM bytes of one
         # launch — read yhat f32 [B,H,N] + w_prev f64 [B,N]; write W0 f64 [B,N] + status i32 +
         # value f64 + iters i32 per window — over its HIP-event launch time, against 8 TB/s.
@@ -774,34 +845,9 @@ def main():
         latpow = B >= LATPOW_MINB
         lat_flops = 2.0 * B * H * N * L + 2.0 * H * N * L * L if latpow else 2.0 * B * H * (L * L + L * N)
         roll_flops = 2.0 * B * (obs * args.hidden + args.hidden * args.hidden + args.hidden * L) + lat_flops
-        c4 = world > 1
-        line = {
-            "metric": METRIC, "value": value, "unit": "windows/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong" if c4 else "weak", "vs_baseline": None,
-            "dtype": "f32 rollout (fp32 GEMMs as three exact bf16 planes); mixed f32->f64 IPM solve "
-                     "(float32 phase to mu 3e-5, float64 finish: stopping rule, status and W in float64)",
-            "data": "synthetic (seeded N(0,1) standardized embeddings, Dirichlet w_prev, random-init finance_sparse weights)",
-            "config": {"workload": (f"C4 (BASELINE configs[3]): {G} windows/step over {world} GPUs" if c4 else
-                                    f"C3 (BASELINE configs[2]): {G} windows/GPU") +
-                                   f", {N} assets, latent {L}, H={H}, obs {obs}, GenericKM enc "
-                                   f"[{args.hidden},{args.hidden}], L1-turnover MPC c=1e-3 tau=0.2 no-short",
-                       "windows_per_gpu": B, "global_windows_per_step": G,
-                       "parallelism": ((f"windows sharded over {world} ranks sharing cuda:0 (readiness check, not "
-                                        f"a scaling figure), {args.backend} gather of W0 to rank 0")
-                                       if args.share_device and c4 else
-                                       f"windows sharded over {world} GPUs (contiguous blocks of one global "
-                                       f"stream), {'RCCL' if args.backend == 'nccl' else 'gloo'} gather of W0 to rank 0"
-                                       if c4 else "1 GPU, no collective")}
-                      | ({"dist": prov} if prov else {}),
+        line.update({
             "roofline": roof,
             "compute_utilization": util,
-            # SURVEY.md §8(d)'s whole-path bound: compulsory bytes per window = obs (f32 N d) +
-            # w_prev + w0 (f32 as there), weights amortized: windows/s x bytes / 8 TB/s
-            "path_hbm_roofline": {"bound": "hbm", "bytes_per_window": 4 * obs + 8 * N,
-                                  "achieved": value / world * (4 * obs + 8 * N) / 1e9, "peak": HBM_PEAK / 1e9,
-                                  "unit": "GB/s", "frac": value / world * (4 * obs + 8 * N) / HBM_PEAK,
-                                  "ceiling_windows_per_s_per_gpu": HBM_PEAK / (4 * obs + 8 * N)},
             "timed_path": "kmpc_window via DeviceKoopman.window (the KoopmanMPCStrategy.rebalance_batch path); "
                           "kernels: the same step as kmpc_rollout + kmpc_solve, HIP events, after the timed region",
             # rollout: algorithmic fp32 FLOPs / time, against the f32-input MFMA peak; the GEMMs and the
@@ -815,9 +861,7 @@ def main():
                         "rollout_flops_counted": "executed: encoder + " + (
                             "latent powers GEMM (2 L H N per window) + the per-call powers chain (2 H N L^2)"
                             if latpow else "sequential latent loop (2 H (L^2 + L N) per window)")},
-            "solver": {"optimal_or_inaccurate": n_opt, "windows": B,
-                       "mean_ipm_iterations": float(its.float().mean().item())},
-        }
+        })
         line["rollout_parity"] = rollout_parity(model, sd, x, mean_d, std_d, H, N)
         if world == 1 and not args.headline_only:
             line["secondary"] = secondary_c2(dev, args.steps, args.warmup)
@@ -832,6 +876,7 @@ def main():
                                                               min(8.0, args.cpu_seconds / 2))
             line["cpu_baseline_c1"] = cpu_baseline_c1()
             line["cpu_parity"] = parity
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,5 +1,5 @@
-"""bench.py output contract on the GPU: one JSON line with the driver's keys, the roofline and the
-CPU-baseline objects, at a reduced window count (the C3 shape otherwise)."""
+"""bench.py output contract on the GPU: one JSON line with the driver's keys and, with --full, the
+roofline and the CPU-baseline objects, at a reduced window count (the C3 shape otherwise)."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
            "--windows", "2048", "--cpu-seconds", "1"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -33,6 +33,37 @@ def test_bench_json_line_contract():
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1
     # every window of the batch solved (the benchmark never times fallbacks)
     assert rec["solver"]["optimal_or_inaccurate"] == rec["solver"]["windows"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the line is the headline alone (nothing measured after the timed region), and
+    --dump-outputs saves what the last timed step returned, every row at this window count."""
+    import numpy as np
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--windows", "2048", "--dump-outputs", str(d)]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+              "dtype", "config", "solver"):
+        assert k in rec, k
+    for k in ("roofline", "compute_utilization", "kernels", "rollout_parity", "secondary", "cpu_baseline"):
+        assert k not in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["unit"] == "windows/s"
+    assert rec["ms_per_step"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 - 2048) < 1e-6 * 2048
+    assert rec["solver"]["optimal_or_inaccurate"] == rec["solver"]["windows"] == 2048
+    assert sorted(os.listdir(d)) == ["W0.npy", "iters.npy", "status.npy", "value.npy"]
+    W0, val, st, it = (np.load(d / f"{n}.npy") for n in ("W0", "value", "status", "iters"))
+    assert W0.dtype == val.dtype == np.float64 and st.dtype == it.dtype == np.float32
+    assert W0.shape == (2048, 100) and val.shape == st.shape == it.shape == (2048,)
+    assert (st <= 1).all() and (it >= 1).all() and np.isfinite(val).all()
+    # the no-short program: every row of W0 is a portfolio
+    assert W0.min() >= -1e-9 and np.abs(W0.sum(1) - 1).max() < 1e-8
 
 
 @pytest.mark.gpu

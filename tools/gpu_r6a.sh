@@ -16,10 +16,10 @@ for L in "" libkmpc_h0.so libkmpc_h1.so libkmpc_ns.so; do
 done
 LIBS="libkmpc.so libkmpc_ns.so" SHAPES="N=64,H=10|N=30,H=5,cost|C1-shape|N=120,H=10|N=90,H=7|N=200,H=10|N=250,H=10" \
   timeout -k 10 400 bash tools/ab_shapes.sh || exit $?
-timeout -k 10 300 python -u bench.py --global-windows 262144 --headline-only --cpu-seconds 0 --steps 2 --warmup 1 \
+timeout -k 10 300 python -u bench.py --full --global-windows 262144 --headline-only --cpu-seconds 0 --steps 2 --warmup 1 \
   --dump-w0 $O/w0_world1.npy > $O/shard_world1.log 2>&1 || exit $?
 timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --global-windows 262144 --backend gloo --share-device --headline-only \
+  --master-port 29533 bench.py --full --gpus 2 --global-windows 262144 --backend gloo --share-device --headline-only \
   --cpu-seconds 0 --steps 2 --warmup 1 --dump-w0 $O/w0_world2.npy > $O/shard_world2.log 2>&1 || exit $?
 python - > $O/shard_compare.log 2>&1 <<'EOF'
 import numpy as np
@@ -27,5 +27,5 @@ a = np.load("gpurun_out/w0_world1.npy"); b = np.load("gpurun_out/w0_world2.npy")
 print("shapes", a.shape, b.shape, "bit-identical", bool(np.array_equal(a, b)), "max|d|", float(np.abs(a - b).max()))
 EOF
 rm -f $O/w0_world1.npy $O/w0_world2.npy
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || exit $?
 echo "exit 0"

@@ -12,5 +12,5 @@ for L in "" libkmpc_rf0.so "" libkmpc_rf0.so; do
 done
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread -rf > $O/gputests.log 2>&1
 rc=$?; echo "gputests rc $rc"; [ $rc -le 1 ] || exit $rc
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || exit $?
 echo "exit 0"

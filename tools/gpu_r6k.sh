@@ -18,7 +18,7 @@ cp $P/libkmpc.so $P/libkmpc_new.so
 for L in new old new old; do
   cp $P/libkmpc_$L.so $P/libkmpc.so
   echo "== $L" >> $O/r6k_bench.log
-  timeout -k 10 300 python -u bench.py --headline-only >> $O/r6k_bench.log 2>>$O/r6k_bench.err || exit $?
+  timeout -k 10 300 python -u bench.py --full --headline-only >> $O/r6k_bench.log 2>>$O/r6k_bench.err || exit $?
 done
 cp $P/libkmpc_new.so $P/libkmpc.so
 echo "exit 0"

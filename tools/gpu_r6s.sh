@@ -12,7 +12,7 @@ cp $P/libkmpc.so $P/libkmpc_prod.so
 for L in prod im5 im4 prod im5 im4; do
   cp $P/libkmpc_$L.so $P/libkmpc.so
   echo "== $L" >> $O/r6s_bench.log
-  timeout -k 10 400 python -u bench.py --cpu-seconds 0 >> $O/r6s_bench.log 2>>$O/r6s_bench.err || exit $?
+  timeout -k 10 400 python -u bench.py --full --cpu-seconds 0 >> $O/r6s_bench.log 2>>$O/r6s_bench.err || exit $?
 done
 cp $P/libkmpc_prod.so $P/libkmpc.so
 : > $O/r6s_c5.log

@@ -12,7 +12,7 @@ cp $P/libkmpc.so $P/libkmpc_prod.so
 for L in prod oldrule prod oldrule; do
   cp $P/libkmpc_$L.so $P/libkmpc.so
   echo "== $L" >> $O/r6u_bench.log
-  timeout -k 10 400 python -u bench.py --cpu-seconds 0 >> $O/r6u_bench.log 2>>$O/r6u_bench.err || exit $?
+  timeout -k 10 400 python -u bench.py --full --cpu-seconds 0 >> $O/r6u_bench.log 2>>$O/r6u_bench.err || exit $?
 done
 cp $P/libkmpc_prod.so $P/libkmpc.so
 : > $O/r6u_c5.log

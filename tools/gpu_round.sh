@@ -5,11 +5,11 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="python bench.py --cpu-seconds 0 --steps 3 --warmup 1"
+B="python bench.py --full --cpu-seconds 0 --steps 3 --warmup 1"
 O=gpurun_out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $O/gputests.log 2>&1 &&
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 400 python bench.py > $O/bench.log 2>$O/bench.err &&
+timeout -k 10 400 python bench.py --full > $O/bench.log 2>$O/bench.err &&
 timeout -k 10 60 tools/dev/f64_peak > $O/f64_peak.log 2>&1 &&
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- $B > $O/prof.log 2>&1 &&
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run -- $B > $O/pmc_fetch.log 2>&1 &&

@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="python bench.py --cpu-seconds 0 --steps 3 --warmup 1"
+B="python bench.py --full --cpu-seconds 0 --steps 3 --warmup 1"
 BH="$B --headline-only"   # (the PMC passes: the headline step only)
 O=gpurun_out
 timeout -k 10 60 tools/dev/f64_peak > $O/f64_peak.log 2>&1 &&

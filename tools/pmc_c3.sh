@@ -3,7 +3,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="python bench.py --cpu-seconds 0 --steps 3 --warmup 1"
+B="python bench.py --full --cpu-seconds 0 --steps 3 --warmup 1"
 O=gpurun_out
 timeout -k 10 60 tools/dev/f64_peak > $O/f64_peak.log 2>&1 &&
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run -- $B > $O/pmc_fetch.log 2>&1 &&
