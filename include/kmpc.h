@@ -273,6 +273,36 @@ int kmpc_backtest_run(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sde
                       const float* yhat, const float* realized, int n_real, double* weights, double* value,
                       double* hist, double* target, int* status, double* obj, void* stream);
 
+/* A hyper-parameter sweep of kmpc_backtest_run in ONE launch (ABI 0.7.0): n_cfg configs — each an
+ * MPCConfig.cost_coeff, an MPCConfig.max_turnover and a BacktestConfig.cost_coeff — over the same
+ * desc->P paths, one workgroup (one lane group in the packed form) per (config j, path p). Results
+ * are config-major: row j * P + p of weights / value / hist / target / status / obj. The forecasts
+ * and the realized returns depend on the path only and are shared by the configs, not replicated.
+ *   desc:     P = paths; cost_coeff is ignored (bt_cost[j] instead).
+ *   sdesc:    the solve's program; cost_coeff, max_turnover and B are ignored; allow_short and
+ *             return_full_W must be 0.
+ *   mpc_cost, max_turnover, bt_cost: [n_cfg] float64 DEVICE arrays. The kernels are the constant
+ *             case "no short, cost and cap": a config with max_turnover[j] <= 0, mpc_cost[j] < 0 or
+ *             a non-finite parameter is outside it, and since the host cannot see the values, every
+ *             step of that config ends KMPC_STATUS_SOLVER_ERROR with the hold fallback (W0 = w_prev:
+ *             turnover and cost 0); the other configs are not affected. Callers run such configs
+ *             through kmpc_backtest_run / the lock-step loop instead.
+ *   yhat:     [n_steps, P, H, N] float32, realized: [n_steps, P, N] float32, n_real: as kmpc_backtest_run.
+ *   weights [n_cfg,P,N] f64, value [n_cfg,P] f64, hist [n_cfg,P,S,4]: updated in place.
+ *   target [n_cfg*P,N] f64, status [n_cfg*P] int, obj [n_cfg*P] f64: scratch, as kmpc_backtest_run.
+ * Argument rules and return codes as kmpc_backtest_run (n_steps = 0 is the shape probe); n_cfg < 1
+ * is KMPC_ERR_INVALID. Always float64, at every batch size: precision AUTO or F64; MIXED is
+ * KMPC_ERR_UNSUPPORTED. Shapes: those of kmpc_backtest_run (H = 10 or 5 with 32 < N <= 256; N <= 32
+ * with H = 2, 5 or 10, packed or one per wave as kmpc_solve would run a batch of n_cfg * P windows),
+ * KMPC_ERR_UNSUPPORTED elsewhere. Config j's rows are bit-identical to kmpc_backtest_run with that
+ * config's parameters wherever both pick the same kernel. kmpc_backtest_metrics takes the result
+ * with desc.P = n_cfg * P. */
+int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
+                        const double* mpc_cost, const double* max_turnover, const double* bt_cost,
+                        int step0, int n_steps, const float* yhat, const float* realized, int n_real,
+                        double* weights, double* value, double* hist, double* target, int* status,
+                        double* obj, void* stream);
+
 /* metrics [P,5]: Sharpe Ratio, Max Drawdown, Avg Turnover, Final Value, Total Return. */
 int kmpc_backtest_metrics(const kmpc_backtest_desc* desc, const double* hist, double* metrics,
                           void* stream);
@@ -337,7 +367,8 @@ const char* kmpc_strerror(int code);
    (KMPC_PRECISION_MIXED, KMPC_DTYPE_F32_F32MFMA; AUTO precision now float64 below KMPC_MIXED_MIN_B
    windows; KMPC_DTYPE_F32's GEMMs on three bf16 planes), no layout change. 0.5.0 added a function
    (kmpc_backtest_run), no layout change. 0.6.0 added enum values only (KMPC_LATENT_SEQUENTIAL) and
-   kmpc_backtest_run's packed shapes, no layout change. */
+   kmpc_backtest_run's packed shapes, no layout change. 0.7.0 added a function
+   (kmpc_backtest_sweep), no layout change. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

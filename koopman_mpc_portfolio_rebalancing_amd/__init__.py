@@ -9,6 +9,7 @@ from .mpc import (MPCConfig, gross_returns, log_utility_value_batched, solve_mpc
                   solve_mpc_log_utility_batched, solve_mpc_mean_variance, solve_mpc_mean_variance_batched)
 from .koopman import DeviceKoopman, KoopmanModelSpec, standardize_panel  # noqa: F401
 from .backtest import (BacktestConfig, BuyAndHoldStrategy, KoopmanMPCStrategy, Strategy,  # noqa: F401
-                       calculate_metrics, run_backtest, run_backtest_lockstep)
+                       calculate_metrics, run_backtest, run_backtest_lockstep, run_backtest_sweep,
+                       sweep_backtest)
 
-__version__ = "0.6.0"
+__version__ = "0.7.0"

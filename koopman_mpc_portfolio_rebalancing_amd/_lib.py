@@ -35,7 +35,8 @@ KMPC_MV_MAX_H = 16
 EXPORTED_SYMBOLS = ("kmpc_solve", "kmpc_rollout", "kmpc_window", "kmpc_workspace_bytes",
                     "kmpc_backtest_step", "kmpc_backtest_metrics", "kmpc_standardize", "kmpc_strerror",
                     "kmpc_version", "kmpc_solve_mv", "kmpc_rolling_moments", "kmpc_solve_mv_ws",
-                    "kmpc_mv_workspace_bytes", "kmpc_gross_returns", "kmpc_backtest_run")
+                    "kmpc_mv_workspace_bytes", "kmpc_gross_returns", "kmpc_backtest_run",
+                    "kmpc_backtest_sweep")
 
 PATH_AUTO, PATH_REGISTER, PATH_LARGE, PATH_REGISTER_UNPACKED = 0, 1, 2, 3   # kmpc_solve_desc.path
 PRECISION_AUTO, PRECISION_F64, PRECISION_MIXED = 0, 1, 2   # kmpc_solve_desc.precision
@@ -46,8 +47,8 @@ PACK_MIN_B = 512     # KMPC_PACK_MIN_B: AUTO packs N <= 32 windows 2-4 per wave 
 # kmpc_rollout_desc.latent_unfused, 0.3.0 kmpc_solve_desc.precision and .mu_handoff, so an older
 # library would read them past its structs' end; 0.4.0 added enum values only (KMPC_PRECISION_MIXED,
 # KMPC_DTYPE_F32_F32MFMA), no layout change; 0.5.0 added kmpc_backtest_run;
-# 0.6.0 enum values only (KMPC_LATENT_SEQUENTIAL)
-ABI_VERSION = "0.6.0"
+# 0.6.0 enum values only (KMPC_LATENT_SEQUENTIAL); 0.7.0 added kmpc_backtest_sweep
+ABI_VERSION = "0.7.0"
 
 
 class KmpcError(RuntimeError):
@@ -115,6 +116,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     L.kmpc_backtest_run.argtypes = [ctypes.POINTER(BacktestDesc), ctypes.POINTER(SolveDesc), ctypes.c_int,
                                     ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_backtest_run.restype = ctypes.c_int
+    L.kmpc_backtest_sweep.argtypes = [ctypes.POINTER(BacktestDesc), ctypes.POINTER(SolveDesc), ctypes.c_int, vp, vp,
+                                      vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp,
+                                      vp]
+    L.kmpc_backtest_sweep.restype = ctypes.c_int
     L.kmpc_backtest_metrics.argtypes = [ctypes.POINTER(BacktestDesc), vp, vp, vp]
     L.kmpc_backtest_metrics.restype = ctypes.c_int
     L.kmpc_standardize.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]

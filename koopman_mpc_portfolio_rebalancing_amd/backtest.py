@@ -393,3 +393,185 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
     return {"portfolio_value": hist[..., 0], "return": hist[..., 1], "turnover": hist[..., 2],
             "cost": hist[..., 3], "weights": w,
             "metrics": {name: metrics[:, j] for j, name in enumerate(METRIC_NAMES)} if S else {}}
+
+
+def _sweep_fields(cfg, free) -> Dict[str, Any]:
+    import dataclasses
+    d = dataclasses.asdict(cfg) if dataclasses.is_dataclass(cfg) else dict(vars(cfg))
+    return {k: v for k, v in d.items() if k not in free}
+
+
+def _sweep_configs(mpc_configs) -> list:
+    """The configs of a sweep: they may differ in cost_coeff and max_turnover only (the kernel's
+    per-config parameters); cost_coeff >= 0 as _solve_desc asks. Raises ValueError, no device work."""
+    cfgs = list(mpc_configs)
+    if not cfgs:
+        raise ValueError("mpc_configs is empty")
+    f0 = _sweep_fields(cfgs[0], ("cost_coeff", "max_turnover"))
+    for j, c in enumerate(cfgs):
+        fj = _sweep_fields(c, ("cost_coeff", "max_turnover"))
+        if fj != f0:
+            diff = sorted(k for k in set(f0) | set(fj) if f0.get(k) != fj.get(k))
+            raise ValueError(f"mpc_configs[{j}] differs from mpc_configs[0] in {diff}: a sweep varies "
+                             "cost_coeff and max_turnover only")
+        if float(c.cost_coeff) < 0:
+            raise ValueError(f"cost_coeff must be >= 0 (got {c.cost_coeff}): the problem is not convex")
+    return cfgs
+
+
+def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: BacktestConfig, mean, std,
+                       mpc_configs: Sequence[MPCConfig], bt_cost_coeffs: Optional[Sequence[float]] = None,
+                       n_rows: Optional[int] = None) -> Dict[str, Any]:
+    """A hyper-parameter sweep of run_backtest_lockstep: C configs (MPCConfig.cost_coeff,
+    MPCConfig.max_turnover, BacktestConfig.cost_coeff) over the same P paths, every step of every
+    (config, path) in kmpc_backtest_sweep launches — one workgroup or lane group each, so at small P
+    the configs fill the slots a single backtest leaves idle. The forecasts depend on the
+    observations only: they are rolled out once per chunk for the P paths (PREROLL_CHUNK // P steps,
+    as the persistent run does it) and shared by the configs.
+
+    Args:
+        strategy: its model is used; the solve's program comes from mpc_configs.
+        obs, realized, mean, std, n_rows: as run_backtest_lockstep.
+        config: BacktestConfig (initial_capital, horizon, rebalance_freq; cost_coeff is the default
+            of bt_cost_coeffs).
+        mpc_configs: C MPCConfigs that differ in cost_coeff and max_turnover only (ValueError otherwise).
+        bt_cost_coeffs: the bookkeeping's cost_coeff per config (default config.cost_coeff for all).
+    Configs the kernel cannot take (max_turnover <= 0 or a non-finite parameter: another constraint
+    case; every config where the C ABI has no sweep kernel for the shape) run as one
+    run_backtest_lockstep call each. Config j's rows equal run_backtest_lockstep(..., persistent=True)
+    with that config bit for bit wherever both run the same kernel.
+    Returns: the run_backtest_lockstep dict with a leading config axis — portfolio_value / return /
+        turnover / cost [C, P, S], weights [C, P, N], metrics {name: [C, P]} — and "in_kernel", a bool
+        [C] (CPU): the configs the sweep kernel ran.
+    """
+    import copy
+    import math
+    cfgs = _sweep_configs(mpc_configs)
+    C = len(cfgs)
+    btc = [float(config.cost_coeff)] * C if bt_cost_coeffs is None else [float(v) for v in bt_cost_coeffs]
+    if len(btc) != C:
+        raise ValueError(f"bt_cost_coeffs has {len(btc)} entries for {C} configs")
+    km = strategy.device_model()
+    dev = km.device
+    x = torch.as_tensor(obs).to(dev, torch.float32)
+    r = torch.as_tensor(realized).to(dev, torch.float32).contiguous()
+    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2]:
+        raise ValueError("obs must be [P, T, obs] and realized [P, T, N]")
+    P, T, N = r.shape
+    n_rows = T if n_rows is None else int(n_rows)
+    steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
+    S = len(steps)
+    H = int(cfgs[0].horizon)
+    kern = [j for j, c in enumerate(cfgs) if float(c.max_turnover) > 0 and math.isfinite(float(c.max_turnover))
+            and math.isfinite(float(c.cost_coeff))]
+    Ck = len(kern)
+    L = _lib.load()
+    w = torch.full((Ck, P, N), 1.0 / N, dtype=torch.float64, device=dev)
+    value = torch.full((Ck, P), float(config.initial_capital), dtype=torch.float64, device=dev)
+    hist = torch.empty((Ck, P, max(S, 1), 4), dtype=torch.float64, device=dev)
+    metrics = torch.empty((Ck * P, 5), dtype=torch.float64, device=dev)
+
+    def run_kernel() -> bool:
+        """False (nothing run) where the C ABI has no sweep kernel for this shape."""
+        d = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
+        sdesc = _solve_desc(Ck * P, N, H, cfgs[0], False)
+        f64 = dict(dtype=torch.float64, device=dev)
+        pc = torch.tensor([float(cfgs[j].cost_coeff) for j in kern], **f64)
+        pt = torch.tensor([float(cfgs[j].max_turnover) for j in kern], **f64)
+        pb = torch.tensor([btc[j] for j in kern], **f64)
+        target = torch.empty((Ck * P, N), **f64)
+        status = torch.empty((Ck * P,), dtype=torch.int32, device=dev)
+        objv = torch.empty((Ck * P,), **f64)
+        sh = _lib.stream_handle(dev)
+
+        def call(k0, n, y, rr, n_real):
+            return L.kmpc_backtest_sweep(ctypes.byref(d), ctypes.byref(sdesc), Ck, pc.data_ptr(), pt.data_ptr(),
+                                         pb.data_ptr(), k0, n, y, rr, n_real, w.data_ptr(), value.data_ptr(),
+                                         hist.data_ptr(), target.data_ptr(), status.data_ptr(), objv.data_ptr(), sh)
+
+        rc = call(0, 0, None, None, 0)   # (shape check only)
+        if rc == _lib.KMPC_ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc)
+        xt = x.transpose(0, 1).contiguous()
+        rt = r.transpose(0, 1).contiguous()
+        m, sd = km._stats(mean, std, N)
+        sc = max(1, PREROLL_CHUNK // P)          # steps per batched rollout
+        steps_t = torch.as_tensor(steps, dtype=torch.long, device=dev)
+        for k0 in range(0, S, sc):
+            n = min(sc, S - k0)
+            y = km.rollout(xt[steps_t[k0:k0 + n]].reshape(n * P, -1), m, sd, H, N).contiguous()
+            tn = steps_t[k0:k0 + n] + 1
+            n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
+            rr = rt[tn[:n_real]].contiguous() if n_real else None
+            _lib.check(call(k0, n, y.data_ptr(), rr.data_ptr() if rr is not None else None, n_real))
+        dm = _lib.BacktestDesc(Ck * P, N, max(S, 1), 0.0)
+        _lib.check(L.kmpc_backtest_metrics(ctypes.byref(dm), hist.data_ptr(), metrics.data_ptr(), sh))
+        return True
+
+    with torch.cuda.device(dev):
+        if not (Ck and P and S and run_kernel()):
+            kern, Ck = [], 0
+            w, hist, metrics = w[:0], hist[:0], metrics[:0]
+    in_kernel = torch.zeros(C, dtype=torch.bool)
+    if kern:
+        in_kernel[kern] = True
+    cols = ("portfolio_value", "return", "turnover", "cost")
+    hist = hist[:, :, :S]
+    metrics = metrics.reshape(Ck, P, 5)
+    if Ck < C:   # the kernel's rows and each other config's own lock-step run, in the configs' order
+        full_h = torch.empty((C, P, S, 4), dtype=torch.float64, device=dev)
+        full_w = torch.empty((C, P, N), dtype=torch.float64, device=dev)
+        full_m = torch.empty((C, P, 5), dtype=torch.float64, device=dev)
+        if Ck:
+            ki = torch.as_tensor(kern, device=dev)
+            full_h[ki], full_w[ki], full_m[ki] = hist, w, metrics
+        for j in range(C):
+            if not in_kernel[j]:
+                bcfg = copy.copy(config)
+                bcfg.cost_coeff = btc[j]
+                o = run_backtest_lockstep(KoopmanMPCStrategy(km, cfgs[j]), x, r, bcfg, mean, std, n_rows=n_rows)
+                full_w[j] = o["weights"]
+                for i, k in enumerate(cols):
+                    full_h[j, :, :, i] = o[k]
+                for i, name in enumerate(METRIC_NAMES):
+                    if S:
+                        full_m[j, :, i] = o["metrics"][name]
+        hist, w, metrics = full_h, full_w, full_m
+    out = {k: hist[..., i] for i, k in enumerate(cols)}
+    out["weights"] = w
+    out["metrics"] = {name: metrics[..., i] for i, name in enumerate(METRIC_NAMES)} if S else {}
+    out["in_kernel"] = in_kernel
+    return out
+
+
+def sweep_backtest(strategy: KoopmanMPCStrategy, env: Any, config: BacktestConfig, mpc_configs: Sequence[MPCConfig],
+                   bt_configs: Optional[Sequence[BacktestConfig]] = None) -> list:
+    """run_backtest(KoopmanMPCStrategy(model, mpc_configs[j]), env, bt_configs[j]) for C configs on one
+    environment in one sweep (run_backtest_sweep with P = 1): the reference's single-environment call,
+    its hand-fixed hyper-parameters (MPCConfig.cost_coeff, MPCConfig.max_turnover,
+    BacktestConfig.cost_coeff) swept. bt_configs (default: config for every entry) may differ from
+    config in cost_coeff only. Returns C DataFrames with the reference's columns (date,
+    portfolio_value, return, turnover, cost), the rebalance_freq quirk kept. An env without stats
+    (custom de-standardisation) runs run_backtest per config."""
+    cfgs = _sweep_configs(mpc_configs)
+    bts = [config] * len(cfgs) if bt_configs is None else list(bt_configs)
+    if len(bts) != len(cfgs):
+        raise ValueError(f"bt_configs has {len(bts)} entries for {len(cfgs)} configs")
+    f0 = _sweep_fields(config, ("cost_coeff",))
+    for j, b in enumerate(bts):
+        if _sweep_fields(b, ("cost_coeff",)) != f0:
+            raise ValueError(f"bt_configs[{j}] differs from config in more than cost_coeff")
+    st = _env_stats(env)
+    if st is None:
+        km = strategy.device_model()
+        return [run_backtest(KoopmanMPCStrategy(km, c), env, b, verbose=False) for c, b in zip(cfgs, bts)]
+    data = env.test_dataset.data
+    rets = env.destandardize_returns(env.extract_current_returns(data))
+    n_rows = len(env.test_dataset)
+    out = run_backtest_sweep(strategy, torch.as_tensor(data)[None], torch.as_tensor(rets)[None], config, st[0], st[1],
+                             cfgs, [float(b.cost_coeff) for b in bts], n_rows=n_rows)
+    steps = range(0, n_rows - config.horizon, config.rebalance_freq)
+    dates = [env.test_dataset.dates[t] for t in steps]
+    cols = {k: out[k][:, 0].cpu().numpy() for k in ("portfolio_value", "return", "turnover", "cost")}
+    return [pd.DataFrame({"date": dates, **{k: v[j] for k, v in cols.items()}}) for j in range(len(cfgs))]

@@ -48,6 +48,7 @@ bt_run_kernel(SolveArgs a0, BtRun r) {
             // out of the loop — cut the scratch from 512 to 448 B per lane but ran slower: P = 64
             // 0.898 -> 0.913 ms per step, P = 1,024 1.92 -> 1.98 ms)
             const int b = blockIdx.x * WPB + grp<GL>();
+            const int yb = b;
 #include "kmpc_ipm_body.inc"
         }
         __syncthreads();   // W0 (st.target) of every lane, and the solve's LDS, done

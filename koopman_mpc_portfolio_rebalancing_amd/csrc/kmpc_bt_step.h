@@ -33,7 +33,9 @@ struct StepArgs {
 };
 
 // path p's step a.k; red: >= blockDim / 64 doubles of LDS. Every thread of the block calls it.
-__device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, double* red) {
+// pr: the row of a.realized the path reads (p itself, or in the sweep kernel, kmpc_bt_sweep.h, the
+// environment path that the configs share).
+__device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, int pr, double* red) {
     const double* tg = a.target + (size_t)p * a.N;
     double* w = a.w + (size_t)p * a.N;
     double tv = 0.0;
@@ -44,7 +46,7 @@ __device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, double* r
     value -= cost;
     double port = 0.0;
     if (a.realized) {
-        const float* y = a.realized + (size_t)p * a.N;
+        const float* y = a.realized + (size_t)pr * a.N;
         double pv = 0.0;
         for (int i = threadIdx.x; i < a.N; i += blockDim.x) {
             const float r = np_expf(y[i]) - 1.0f;
@@ -71,6 +73,8 @@ __device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, double* r
     }
 }
 
+__device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, double* red) { bt_step_body(a, p, p, red); }
+
 // The same step for a path on a GL-lane group of a packed wave (N <= GL, lane i owns asset i):
 // the lock-step kernel's sums restricted to the group. There (one 64-lane wave for N <= 64) the
 // butterfly levels at and above GL add exact zeros (lanes past N hold 0), and the levels below GL
@@ -84,7 +88,7 @@ __device__ __forceinline__ double group_sum_bt(double v) {
 }
 
 template <int GL>
-__device__ __forceinline__ void bt_step_group(const StepArgs& a, int p, int i) {
+__device__ __forceinline__ void bt_step_group(const StepArgs& a, int p, int pr, int i) {
     const double* tg = a.target + (size_t)p * a.N;
     double* w = a.w + (size_t)p * a.N;
     const bool on = i < a.N;
@@ -96,7 +100,7 @@ __device__ __forceinline__ void bt_step_group(const StepArgs& a, int p, int i) {
     value -= cost;
     double port = 0.0;
     if (a.realized) {
-        const float y = on ? a.realized[(size_t)p * a.N + i] : 0.0f;
+        const float y = on ? a.realized[(size_t)pr * a.N + i] : 0.0f;
         const float r = np_expf(y) - 1.0f;
         port = group_sum_bt<GL>(on ? 0.0 + tgi * (double)r : 0.0);
         value *= (1.0 + port);
@@ -116,6 +120,9 @@ __device__ __forceinline__ void bt_step_group(const StepArgs& a, int p, int i) {
         h[3] = cost;
     }
 }
+
+template <int GL>
+__device__ __forceinline__ void bt_step_group(const StepArgs& a, int p, int i) { bt_step_group<GL>(a, p, p, i); }
 
 }  // namespace bt
 }  // namespace kmpc

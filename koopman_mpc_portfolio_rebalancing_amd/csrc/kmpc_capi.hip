@@ -26,7 +26,7 @@ int check_solve(const kmpc_solve_desc* d) {
 
 extern "C" {
 
-const char* kmpc_version(void) { return "kmpc 0.6.0 (gfx950)"; }
+const char* kmpc_version(void) { return "kmpc 0.7.0 (gfx950)"; }
 
 const char* kmpc_strerror(int code) {
     switch (code) {
@@ -135,6 +135,29 @@ int kmpc_backtest_run(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sde
         return KMPC_ERR_INVALID;
     return kmpc::backtest_run_launch(desc, &sd, step0, n_steps, yhat, realized, n_real, weights, value, hist,
                                      target, status, obj, (hipStream_t)stream);
+}
+
+int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
+                        const double* mpc_cost, const double* max_turnover, const double* bt_cost, int step0,
+                        int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
+                        double* value, double* hist, double* target, int* status, double* obj, void* stream) {
+    if (!desc || !sdesc || desc->P < 0 || desc->N < 1 || desc->S < 1 || step0 < 0 || n_steps < 0 ||
+        step0 + n_steps > desc->S || n_real < 0 || n_real > n_steps || sdesc->N != desc->N || n_cfg < 1 ||
+        (long long)n_cfg * desc->P > 0x7fffffffLL)
+        return KMPC_ERR_INVALID;
+    kmpc_solve_desc sd = *sdesc;   // (the batch is configs x paths; the configs carry c and tau)
+    sd.B = n_cfg * desc->P;
+    sd.cost_coeff = 0.0;
+    sd.max_turnover = 1.0;
+    const int rc = check_solve(&sd);
+    if (rc) return rc;
+    if (desc->P > 0 && n_steps > 0 &&
+        (!mpc_cost || !max_turnover || !bt_cost || !yhat || !weights || !value || !hist || !target || !status ||
+         !obj || (n_real > 0 && !realized)))
+        return KMPC_ERR_INVALID;
+    return kmpc::backtest_sweep_launch(desc, &sd, n_cfg, mpc_cost, max_turnover, bt_cost, step0, n_steps, yhat,
+                                       realized, n_real, weights, value, hist, target, status, obj,
+                                       (hipStream_t)stream);
 }
 
 int kmpc_standardize(int T, int N, const double* log_returns, const double* mean, const double* std,

@@ -16,6 +16,11 @@ int backtest_run_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd,
                         const float* yhat, const float* realized, int n_real, double* weights, double* value,
                         double* hist, double* target, int* status, double* obj, hipStream_t stream);
 
+int backtest_sweep_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const double* mpc_cost,
+                          const double* max_turnover, const double* bt_cost, int step0, int n_steps,
+                          const float* yhat, const float* realized, int n_real, double* weights, double* value,
+                          double* hist, double* target, int* status, double* obj, hipStream_t stream);
+
 // kmpc_backtest.hip
 int gross_returns_launch(size_t n, const float* yhat, float* R, hipStream_t stream);
 int backtest_step_launch(const kmpc_backtest_desc* d, int step, const double* target,

@@ -3,7 +3,8 @@
 // once per step). An include rather than a function: ipm_kernel's instruction stream stays exactly
 // what it was (a call boundary, even inlined, reshuffles this kernel's register allocation).
 // Names in scope at the include: HM, MAXT, EXACT, FL, CS, QL, GL, PH (template parameters), Real,
-// NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window).
+// NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window: w_prev, outputs, warm record),
+// yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h).
     if constexpr (PH == 3) {   // the retry pass: only windows whose warm start did not end optimal
         if (reinterpret_cast<const int*>(args.warm + (size_t)b * args.warm_floats)[0] != 3) return;
     }
@@ -21,7 +22,7 @@
     T.tau = args.tau;
     const int H = T.H, N = T.N;
     const double* wp = args.wp + (size_t)b * N;   // (H is a compile-time constant when EXACT)
-    const float* yh = args.yhat + (size_t)b * H * N;
+    const float* yh = args.yhat + (size_t)yb * H * N;
     T.wpi = T.act ? wp[T.i] : Real(0.0);
 
     // ---- inputs: m = R - 1 with R = np.exp(yhat) in float32 (mpc.py:55), objective scale,

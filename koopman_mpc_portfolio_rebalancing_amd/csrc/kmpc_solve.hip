@@ -446,4 +446,50 @@ int backtest_run_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd,
 #endif
 }
 
+// kmpc_backtest_sweep: n_cfg configs over the same bd->P paths in one launch of the sweep form of
+// the path-persistent kernel (kmpc_bt_sweep.h), for the shapes backtest_run_launch covers. The
+// configs' parameters are device arrays, so the constraint case cannot depend on them: always the
+// constant case 7 in float64 (no mixed pair at any batch size), packed as pack_small says for a
+// batch of n_cfg P windows. sd's cost_coeff, max_turnover and B are not read.
+int backtest_sweep_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const double* mpc_cost,
+                          const double* max_turnover, const double* bt_cost, int step0, int n_steps,
+                          const float* yhat, const float* realized, int n_real, double* weights, double* value,
+                          double* hist, double* target, int* status, double* obj, hipStream_t stream) {
+    kmpc_solve_desc d = *sd;
+    d.B = n_cfg * bd->P;
+    d.cost_coeff = 0.0;
+    d.max_turnover = 1.0;   // (case 7; the kernel reads the configs' own)
+    SolveArgs a = make_args(&d);
+    const bool packed = pack_small(a);
+    if (a.return_full || a.allow_short || use_big(a) || d.precision == KMPC_PRECISION_MIXED || a.N > 256)
+        return KMPC_ERR_UNSUPPORTED;
+    if (packed ? (a.H != 2 && a.H != 5 && a.H != 10) : (a.H != 10 && a.H != 5)) return KMPC_ERR_UNSUPPORTED;
+    if (a.path != KMPC_PATH_AUTO && a.path != KMPC_PATH_REGISTER && a.path != KMPC_PATH_REGISTER_UNPACKED)
+        return KMPC_ERR_UNSUPPORTED;
+    const int nt = 64 * ((a.N + 63) / 64);
+    const bool c3 = a.H == 10 && nt == 128 && a.N < QL_CS;
+#ifdef KMPC_DEV_ONLY_H10   // (dev builds link the C3 units only)
+    if (packed || !c3) return KMPC_ERR_UNSUPPORTED;
+#endif
+    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
+    a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
+    a.yhat = yhat; a.wp = weights;
+    SweepLaunch l;
+    l.P = bd->P; l.n_steps = n_steps; l.n_real = n_real; l.step0 = step0; l.S = bd->S;
+    l.mpc_cost = mpc_cost; l.max_turnover = max_turnover; l.bt_cost = bt_cost;
+    l.yhat = yhat; l.realized = realized;
+    l.weights = weights; l.value = value; l.hist = hist;
+#ifndef KMPC_DEV_ONLY_H10
+    if (packed)
+        return a.H == 2 ? launch_bt_sweep_packed<2>(a, l, stream)
+                        : (a.H == 5 ? launch_bt_sweep_packed<5>(a, l, stream) : launch_bt_sweep_packed<10>(a, l, stream));
+#endif
+    if (c3) return launch_bt_sweep_c3(a, l, stream);
+#ifndef KMPC_DEV_ONLY_H10
+    return a.H == 5 ? launch_bt_sweep_case<5>(a, l, stream) : launch_bt_sweep_case<10>(a, l, stream);
+#else
+    return KMPC_ERR_UNSUPPORTED;
+#endif
+}
+
 }  // namespace kmpc

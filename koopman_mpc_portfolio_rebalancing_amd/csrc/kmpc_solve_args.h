@@ -63,6 +63,22 @@ int launch_bt_run_case(const SolveArgs& a, int n_steps, int n_real, const float*
 template <int HM>
 int launch_bt_run_packed(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
                          int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream);
+// The sweep form of the path-persistent kernel (kmpc_bt_sweep.h, kmpc_backtest_sweep): a.B = C P
+// work items (config-major), a.wout the [C P, N] W0 scratch, a.status / a.obj [C P] scratch; a.c and
+// a.tau are not read (the kernel takes them per config from the device arrays). Always case 7.
+struct SweepLaunch {
+    int P, n_steps, n_real, step0, S;
+    const double *mpc_cost, *max_turnover, *bt_cost;   // [C] device
+    const float *yhat, *realized;                      // [n_steps, P, H, N], [n_steps, P, N]
+    double *weights, *value, *hist;                    // [C P, N], [C P], [C P, S, 4]
+};
+// ... of the C3 shape (kmpc_solve_c3sw.hip), the constant-case shapes H = HM (kmpc_solve_hsw*.hip)
+// and the packed shapes (kmpc_solve_psw*.hip); KMPC_ERR_UNSUPPORTED elsewhere
+int launch_bt_sweep_c3(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
+template <int HM>
+int launch_bt_sweep_case(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
+template <int HM>
+int launch_bt_sweep_packed(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
 // packed small-window kernels, 64 / GL windows per wave (kmpc_solve_p*.hip); KMPC_ERR_UNSUPPORTED
 // outside N <= 32, 3 H <= 32
 template <int HM>

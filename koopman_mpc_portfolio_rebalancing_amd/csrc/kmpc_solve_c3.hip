@@ -32,6 +32,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(1))) 
     } shu;
     const int b = blockIdx.x;
     if (b >= args.B) return;
+    const int yb = b;
 #if KMPC_REG_HANDOFF_ON
     // the float32 phase's iterate handed to the float64 finish on chip, not
     // through the 20 KB warm record in HBM: each lane's w, s, l1..l3 for its asset and the period

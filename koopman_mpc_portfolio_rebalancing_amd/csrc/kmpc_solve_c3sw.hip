@@ -1,0 +1,11 @@
+// kmpc_solve_c3sw.hip — the sweep form of the path-persistent backtest kernel (kmpc_bt_sweep.h) of
+// the C3 shape (H = 10, N < 104: 128 threads, the LDL^T arrays in LDS), built with the options of
+// kmpc_solve_c3.hip, whose kernel it mirrors.
+#include "kmpc_solve_kernel.h"
+#include "kmpc_bt_sweep.h"
+
+namespace kmpc {
+int launch_bt_sweep_c3(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
+    return launch_bt_sweep_one<10, 128, true, 7, QL_CS, true>(a, l, stream);
+}
+}  // namespace kmpc

@@ -1743,6 +1743,7 @@ __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM 
     auto& sh = shv[grp<GL>()];
     const int b = blockIdx.x * WPB + grp<GL>();
     if (b >= args.B) return;   // (whole groups of the last block)
+    const int yb = b;
 #include "kmpc_ipm_body.inc"
 }
 
