@@ -6,7 +6,11 @@
 // NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window: w_prev, outputs, warm record),
 // yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h).
     if constexpr (PH == 3) {   // the retry pass: only windows whose warm start did not end optimal
+#ifdef KMPC_FUSED_RETRY
+        if (!retry_flag) return;   // (the fused kernel: the float64 finish's verdict, workgroup-uniform)
+#else
         if (reinterpret_cast<const int*>(args.warm + (size_t)b * args.warm_floats)[0] != 3) return;
+#endif
     }
     // waves in the block: a compile-time constant up to 128 threads (the launchers use MAXT = 128
     // only for 128-thread blocks), so the reductions' per-wave slot loops need no run-time guards
@@ -497,6 +501,10 @@
         return;
     }
     __syncthreads();
+#ifdef KMPC_FUSED_RETRY
+    // (thread 0's test below, by every thread: the status comes from workgroup-wide reductions)
+    if constexpr (PH == 2) retry_flag = hand_flag && status != KMPC_STATUS_OPTIMAL;
+#endif
     // ---- outputs: W was written by record_best; fallback (mpc.py:113-115) otherwise ----
     const bool ok = status == KMPC_STATUS_OPTIMAL || status == KMPC_STATUS_OPTIMAL_INACCURATE;
     if (!ok && T.act) {

@@ -4,11 +4,20 @@
 // unit loses 4% at -O2.
 //
 // Also the path-persistent backtest kernel of this shape (kmpc_bt_run.h, kmpc_backtest_run).
+#ifndef KMPC_SCHUR_BCAST_F32   // the Schur LDL^T column in registers, both precisions
+#define KMPC_SCHUR_BCAST_F32 1
+#endif
+#ifndef KMPC_SCHUR_BCAST_F64
+#define KMPC_SCHUR_BCAST_F64 1
+#endif
 #include "kmpc_solve_kernel.h"
 #include "kmpc_bt_run.h"
 
 #ifndef KMPC_REG_HANDOFF_ON   // ipm_mixed_kernel's handoff: 2 LDS, 1 registers, 0 the warm record in HBM
 #define KMPC_REG_HANDOFF_ON 1
+#endif
+#ifndef KMPC_FUSED_RETRY_ON   // ipm_mixed_kernel's retry pass: 1 inside the kernel, 0 the launch of ipm_kernel<..., 3>
+#define KMPC_FUSED_RETRY_ON (KMPC_REG_HANDOFF_ON != 0)
 #endif
 
 namespace kmpc {
@@ -36,8 +45,8 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(1))) 
 #if KMPC_REG_HANDOFF_ON
     // the float32 phase's iterate handed to the float64 finish on chip, not
     // through the 20 KB warm record in HBM: each lane's w, s, l1..l3 for its asset and the period
-    // owners' z4, l4, nu — in the finish's cold-array LDS (2, the default: free during the float32
-    // phase) or in registers (1: live across the phase boundary; 12 more spilled VGPRs in the finish)
+    // owners' z4, l4, nu — in registers (1, the default: live across the phase boundary; 12 more
+    // spilled VGPRs in the finish) or in the finish's cold-array LDS (2: free during the float32 phase)
     static_assert(KMPC_REG_HANDOFF_ON != 2 || (5 * HM * CS + 3 * HM) * 4 <= cold_bytes<HM, MAXT, CS, QL, GL, FL, double>(),
                   "the handoff fits the float64 cold arrays' LDS");
 #if KMPC_REG_HANDOFF_ON == 1
@@ -54,12 +63,30 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(1))) 
 #include "kmpc_ipm_body.inc"
     }();
     __syncthreads();   // the window's header written; the LDS structure reused
+#if KMPC_FUSED_RETRY_ON
+    bool retry_flag = false;
+#define KMPC_FUSED_RETRY
+#endif
     [&]() __attribute__((always_inline)) {
         constexpr int PH = 2;
         using Real = double;
         auto& sh = shu.d;
 #include "kmpc_ipm_body.inc"
     }();
+#if KMPC_FUSED_RETRY_ON
+    // a warm start that did not end optimal (about two windows in 65,536 at the default handoff):
+    // the retry pass by the window's own workgroup, among the other resident windows, instead of
+    // a launch of its own on an otherwise empty GPU. The same body as ipm_kernel<..., 3>.
+    if (!retry_flag) return;
+    __syncthreads();
+    [&]() __attribute__((always_inline)) {
+        constexpr int PH = 3;
+        using Real = double;
+        auto& sh = shu.d;
+#include "kmpc_ipm_body.inc"
+    }();
+#undef KMPC_FUSED_RETRY
+#endif
 #undef KMPC_REG_HANDOFF
 }
 }  // namespace
@@ -77,7 +104,9 @@ int launch_ipm_c3(const SolveArgs& a, hipStream_t stream) {
         const size_t lds = cold_bytes<10, 128, QL_CS, true, 64, 7, double>();
         hipLaunchKernelGGL((ipm_mixed_kernel<10, 128, true, 7, QL_CS, true, 64>), dim3(a.B), dim3(128), lds, stream, a);
         int rc = hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
+#if !KMPC_FUSED_RETRY_ON
         if (rc == KMPC_OK) rc = launch_one<10, 128, true, 7, QL_CS, true, 64, 3>(a, 128, stream);
+#endif
         return rc;
     }
     if (a.warm) {   // mixed precision: the float32 phase, then the float64 finish from its iterates

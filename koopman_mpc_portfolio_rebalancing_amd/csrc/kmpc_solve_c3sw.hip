@@ -1,6 +1,9 @@
 // kmpc_solve_c3sw.hip — the sweep form of the path-persistent backtest kernel (kmpc_bt_sweep.h) of
 // the C3 shape (H = 10, N < 104: 128 threads, the LDL^T arrays in LDS), built with the options of
 // kmpc_solve_c3.hip, whose kernel it mirrors.
+#ifndef KMPC_SCHUR_BCAST_F64   // as kmpc_solve_c3.hip
+#define KMPC_SCHUR_BCAST_F64 1
+#endif
 #include "kmpc_solve_kernel.h"
 #include "kmpc_bt_sweep.h"
 

@@ -426,6 +426,53 @@ __device__ __forceinline__ float row_bcast(float v, int j) {
         default: return dpp_f32<0x15f>(v);
     }
 }
+// g[k] = fma(c_k, nl, g[k]) for k in [K0, K0 + CNT), c_k = lane (k & 15) of ca (k < 16) or cb (k >= 16)
+// in every lane's own 16-lane row: the row_newbcast folded into the FMA's first operand
+// (v_fmac_f32_dpp / v_fmac_f64_dpp, one instruction per element). The compiler does not fold the
+// DPP move itself (gfx9 selects the three-address v_fma, which has no DPP form), so the
+// instructions are written out, in chunks of 8, 4, 2, 1 elements. Each chunk opens with the two
+// wait states a DPP read needs after a VALU write of its source (the hazard the compiler covers
+// for its own DPP moves, not inside asm), so no chunk depends on what was scheduled before it.
+#define KMPC_FD(op, i) "\n\t" op " %[g" #i "], %[c" #i "], %[nl] row_newbcast:%[r" #i "] row_mask:0xf bank_mask:0xf"
+#define KMPC_FD_OUT(i) [g##i] "+v"(g[K0 + i])
+#define KMPC_FD_IN(i) [c##i] "v"(K0 + i < 16 ? ca : cb), [r##i] "n"((K0 + i) & 15)
+#define KMPC_FD_CHUNKS(op)                                                                                          \
+    if constexpr (CNT == 8)                                                                                         \
+        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3) KMPC_FD(op, 4)                    \
+            KMPC_FD(op, 5) KMPC_FD(op, 6) KMPC_FD(op, 7)                                                            \
+            : KMPC_FD_OUT(0), KMPC_FD_OUT(1), KMPC_FD_OUT(2), KMPC_FD_OUT(3), KMPC_FD_OUT(4),                       \
+              KMPC_FD_OUT(5), KMPC_FD_OUT(6), KMPC_FD_OUT(7)                                                        \
+            : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1), KMPC_FD_IN(2), KMPC_FD_IN(3), KMPC_FD_IN(4),              \
+              KMPC_FD_IN(5), KMPC_FD_IN(6), KMPC_FD_IN(7));                                                         \
+    else if constexpr (CNT == 4)                                                                                    \
+        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3)                                   \
+            : KMPC_FD_OUT(0), KMPC_FD_OUT(1), KMPC_FD_OUT(2), KMPC_FD_OUT(3)                                        \
+            : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1), KMPC_FD_IN(2), KMPC_FD_IN(3));                            \
+    else if constexpr (CNT == 2)                                                                                    \
+        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1)                                                                 \
+            : KMPC_FD_OUT(0), KMPC_FD_OUT(1) : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1));                         \
+    else                                                                                                            \
+        asm("s_nop 1" KMPC_FD(op, 0) : KMPC_FD_OUT(0) : [nl] "v"(nl), KMPC_FD_IN(0))
+template <int CNT, int K0, int KM>
+__device__ __forceinline__ void fmac_dpp_chunk(float (&g)[KM], float ca, float cb, float nl) {
+    KMPC_FD_CHUNKS("v_fmac_f32_dpp");
+}
+template <int CNT, int K0, int KM>
+__device__ __forceinline__ void fmac_dpp_chunk(double (&g)[KM], double ca, double cb, double nl) {
+    KMPC_FD_CHUNKS("v_fmac_f64_dpp");
+}
+#undef KMPC_FD_CHUNKS
+#undef KMPC_FD_IN
+#undef KMPC_FD_OUT
+#undef KMPC_FD
+template <int K0, int KM, class T>
+__device__ __forceinline__ void fmac_dpp_from(T (&g)[KM], T ca, T cb, T nl) {
+    constexpr int n = KM - K0, CNT = n >= 8 ? 8 : (n >= 4 ? 4 : (n >= 2 ? 2 : 1));
+    if constexpr (n > 0) {
+        fmac_dpp_chunk<CNT, K0>(g, ca, cb, nl);
+        fmac_dpp_from<K0 + CNT>(g, ca, cb, nl);
+    }
+}
 template <int GL, class T>
 __device__ __forceinline__ T gbcast(T v, int src) {
     if constexpr (GL == 64) {
@@ -442,6 +489,16 @@ __device__ __forceinline__ T gbcast(T v, int src) {
 
 #ifndef KMPC_OPAQUE_LANE
 #define KMPC_OPAQUE_LANE 1
+#endif
+// factor()'s Schur LDL^T column broadcast in registers (one permlane16 swap per step, the DPP
+// row_newbcast inside the FMAs: ldl_steps_dpp) instead of through LDS, per precision; 0 keeps the
+// LDS form. On in the C3 units (kmpc_solve_c3.hip, kmpc_solve_c3sw.hip), where it measured ahead;
+// the other whole-wave units measured behind with it and keep the LDS form.
+#ifndef KMPC_SCHUR_BCAST_F32
+#define KMPC_SCHUR_BCAST_F32 0
+#endif
+#ifndef KMPC_SCHUR_BCAST_F64
+#define KMPC_SCHUR_BCAST_F64 0
 #endif
 #ifndef KMPC_RS_BANK   // bank-masked DPP moves for the row_mirror / row_half_mirror levels
 #define KMPC_RS_BANK 1
@@ -1370,6 +1427,42 @@ __device__ __forceinline__ Real max_step(const TH& T, Shared<HM, NWM, typename T
     return a;
 }
 
+// Steps J .. KM - 1 of factor()'s Schur LDL^T with the column broadcast in registers
+// (KMPC_SCHUR_BCAST_*): whole-wave windows, row r on lane r of wave 0, so the KM <= 32 rows sit on
+// DPP rows 0 and 1. One permlane16 swap per step gives the pair (ca, cb) that carries row 0's /
+// row 1's lanes of the column in both rows, and entry k reaches every lane inside its FMA
+// (fmac_dpp_from) — no ds_write, no wave barrier, no uniform LDS reads, no cv[] array. The same
+// values in the same FMA order as the LDS form in factor(): bit-identical. J is a template
+// parameter (the row_newbcast lane is an immediate), hence the recursion instead of a loop.
+template <int J, int KM, class Real>
+__device__ __forceinline__ void ldl_steps_dpp(Real (&g)[KM], int r, bool& bad, Real& dinv) {
+    static_assert(KM <= 32, "the column sits on two DPP rows");
+    if constexpr (J < KM) {
+        Real u = g[J];   // row r of the updated column J
+        // (written by the previous step's asm FMACs, whose hazards the compiler does not pad: two
+        // wait states before the lane reads below — v_readlane, permlane16 swap, DPP — take it)
+        if constexpr (J > 0) asm("s_nop 1" : "+v"(u));
+        Real ca = u, cb = u;
+        if constexpr (KM > 16 && J + 1 < KM) swap16(ca, cb);
+        const Real d = bcast(u, J);   // the pivot by v_readlane, as the LDS form (from the broadcast: slower)
+        bad = bad || !(d > Real(0.0)) || !(d < huge_of<Real>());
+        const Real dm = fmax(d, tiny_of<Real>());   // 1 / d as in factor()
+        Real id;
+        if constexpr (sizeof(Real) == 8) {
+            id = __builtin_amdgcn_rcp(dm);
+            id = fma(id, fma(-dm, id, Real(1.0)), id);
+            id = fma(id, fma(-dm, id, Real(1.0)), id);
+        } else {
+            id = __builtin_amdgcn_rcpf(dm);
+        }
+        const Real l = (r > J) ? u * id : Real(0.0);  // L_rJ
+        if (r == J) dinv = id;
+        g[J] = l;
+        fmac_dpp_from<J + 1>(g, ca, cb, -l);   // g[k] = fma(-l, c_k, g[k]), k > J
+        ldl_steps_dpp<J + 1>(g, r, bad, dinv);
+    }
+}
+
 // Factor: slack reciprocals, per-asset LDL^T of Q, the Schur matrix G (one Q^{-1} column per
 // pass of a runtime loop), and its Cholesky factor (wave 0). Returns false on breakdown.
 //   G_jl = sum_i c_j c_l (Qi[tj][tl] - [vj] Qi[tj-1][tl] - [vl] Qi[tj][tl-1] + [vj vl] Qi[tj-1][tl-1])
@@ -1625,6 +1718,10 @@ __device__ __forceinline__ bool factor(TH& T, Shared<HM, NWM, typename TH::real_
     // (the column broadcast of the LDL^T steps uses reduction slots: no reduction is in flight here)
     // (two lanes per row — even / odd columns, L_rj to the partner by a permlane32 swap — was
     // bit-identical but measured slower, C3 mixed 79.5 -> 88.0 ms: r06, commit history)
+    // Whole-wave windows (GL = 64) keep the column in registers instead (ldl_steps_dpp) in the
+    // units that set KMPC_SCHUR_BCAST_F32 / _F64, per precision; the packed groups keep the LDS form.
+    constexpr bool DPPCOL = TH::GLN == 64 && KM <= 32 &&
+                            (sizeof(Real) == 4 ? KMPC_SCHUR_BCAST_F32 != 0 : KMPC_SCHUR_BCAST_F64 != 0);
     Real* col = &sh.red[0][0][0];
     if (gvt<TH::GLN>() < WAVE) {
         int r = lane;
@@ -1645,8 +1742,9 @@ __device__ __forceinline__ bool factor(TH& T, Shared<HM, NWM, typename TH::real_
         }
         bool bad = false;
         Real dinv = Real(0.0);
+        if constexpr (DPPCOL) ldl_steps_dpp<0>(g, r, bad, dinv);   // the column in registers: all KM steps
 #pragma unroll
-        for (int j = 0; j < KM; ++j) {
+        for (int j = DPPCOL ? KM : 0; j < KM; ++j) {
             const Real u = g[j];                    // row r of the updated column j
             // the column goes out first and its reads are issued before the pivot reciprocal:
             // the v_rcp_f64 chain runs under the LDS round trip instead of ahead of it
