@@ -129,6 +129,32 @@ int kmpc_solve(const kmpc_solve_desc* desc,
                int*          iters,    /* [B] or NULL */
                void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- MPC solve with a per-asset position limit (added within ABI 0.7.0, see the version note
+ * at the end): the program of kmpc_solve with one more constraint, w_t,i <= max_weight for every
+ * period and asset (0 <= w <= max_weight, no shorting). Arrays, statuses and the fallback are
+ * those of kmpc_solve; a window whose w_prev sits above the limit where the turnover cap does not
+ * let it come down reports KMPC_STATUS_INFEASIBLE and holds. The limit is one more barrier inside
+ * the interior point of the float64 register kernels; the call takes no workspace.
+ * Return codes, all decided before any launch (and before the B == 0 return):
+ *   - desc is checked as for kmpc_solve;
+ *   - max_weight NaN or <= 0: KMPC_ERR_INVALID;
+ *   - max_weight >= 1 without shorting is an inactive bound: the call IS kmpc_solve(desc, ...,
+ *     workspace = NULL, 0) — bit-identical results — and returns KMPC_ERR_WORKSPACE where that
+ *     solve needs a workspace (the large-window kernel, the mixed pair): call kmpc_solve there;
+ *   - N * max_weight <= 1 (an empty feasible set, or the single point 1/N): KMPC_ERR_INVALID;
+ *   - KMPC_ERR_UNSUPPORTED: allow_short != 0; N > 256 or H > 10; path == KMPC_PATH_LARGE;
+ *     precision == KMPC_PRECISION_MIXED.
+ * KMPC_PRECISION_AUTO and _F64 both run float64 at every batch size; batches past 2^22 windows go
+ * as equal launches, as in kmpc_solve. */
+int kmpc_solve_box(const kmpc_solve_desc* desc, double max_weight,
+                   const float*  yhat,     /* [B,H,N] */
+                   const double* w_prev,   /* [B,N]   */
+                   double*       w_out,    /* [B,N] or [B,H,N] */
+                   int*          status,   /* [B] */
+                   double*       obj,      /* [B] */
+                   int*          iters,    /* [B] or NULL */
+                   void* stream);
+
 /* ---- gross returns: R = np.exp(yhat) on float32, bit for bit as numpy 2.x evaluates it on x86-64
  * (mpc.py:55; the realized returns np.exp(r) - 1 of backtest.py:188 use the same function).
  * yhat and R are device arrays of n floats. */
@@ -368,7 +394,10 @@ const char* kmpc_strerror(int code);
    windows; KMPC_DTYPE_F32's GEMMs on three bf16 planes), no layout change. 0.5.0 added a function
    (kmpc_backtest_run), no layout change. 0.6.0 added enum values only (KMPC_LATENT_SEQUENTIAL) and
    kmpc_backtest_run's packed shapes, no layout change. 0.7.0 added a function
-   (kmpc_backtest_sweep), no layout change. */
+   (kmpc_backtest_sweep), no layout change. kmpc_solve_box was added within 0.7.0: a new function
+   only — no struct, enum or existing function changed, so every caller built against 0.7.0 keeps
+   working unchanged and the version string did not move; a caller that needs the function checks
+   for the symbol (dlsym) rather than for a version. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .koopman import DeviceKoopman, KoopmanModelSpec
-from .mpc import MPCConfig, _solve_desc, solve_mpc_log_utility_batched
+from .mpc import MPCConfig, _box_limit, _solve_desc, solve_mpc_log_utility_batched
 
 
 @dataclass
@@ -298,6 +298,12 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
     def run_persistent() -> bool:
         """Every step of every path in kmpc_backtest_run launches (one per rollout chunk of sc steps):
         False (nothing run) where the C ABI has no persistent kernel for this shape."""
+        if _box_limit(strategy.mpc_config, N):
+            # a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it and the
+            # persistent kernel has no box form — the loop's solves go through kmpc_solve_box
+            if explicit:
+                raise ValueError("persistent=True: no persistent backtest kernel for this shape")
+            return False
         sdesc = _solve_desc(P, N, H, strategy.mpc_config, False)
         target = torch.empty((P, N), dtype=torch.float64, device=dev)
         status = torch.empty((P,), dtype=torch.int32, device=dev)
@@ -473,6 +479,8 @@ def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: Back
 
     def run_kernel() -> bool:
         """False (nothing run) where the C ABI has no sweep kernel for this shape."""
+        if _box_limit(cfgs[0], N):   # (equal across the configs, _sweep_configs) no box sweep kernel
+            return False
         d = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
         sdesc = _solve_desc(Ck * P, N, H, cfgs[0], False)
         f64 = dict(dtype=torch.float64, device=dev)

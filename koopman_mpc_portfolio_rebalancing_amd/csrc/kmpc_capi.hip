@@ -64,6 +64,24 @@ int kmpc_solve(const kmpc_solve_desc* desc, const float* yhat, const double* w_p
                               (hipStream_t)stream);
 }
 
+int kmpc_solve_box(const kmpc_solve_desc* desc, double max_weight, const float* yhat, const double* w_prev,
+                   double* w_out, int* status, double* obj, int* iters, void* stream) {
+    // every rule is decided before any launch (and before the B == 0 return)
+    int rc = check_solve(desc);
+    if (rc) return rc;
+    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    // an inactive bound: the plain solve, without a workspace (KMPC_ERR_WORKSPACE if it needs one)
+    if (max_weight >= 1.0 && !desc->allow_short)
+        return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, nullptr, 0, stream);
+    if (!((double)desc->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
+    if (desc->allow_short) return KMPC_ERR_UNSUPPORTED;
+    if (desc->N > 256 || desc->H > 10) return KMPC_ERR_UNSUPPORTED;
+    if (desc->path == KMPC_PATH_LARGE || desc->precision == KMPC_PRECISION_MIXED) return KMPC_ERR_UNSUPPORTED;
+    if (desc->B == 0) return KMPC_OK;
+    if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
+    return kmpc::solve_box_launch(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, (hipStream_t)stream);
+}
+
 /* Debug entry (not part of include/kmpc.h): kmpc_solve plus a per-iteration trace of problem 0,
    trace[4 * it + {0,1,2,3}] = (mu, dual residual, primal residual, step length). */
 int kmpc_solve_trace(const kmpc_solve_desc* desc, const float* yhat, const double* w_prev,

@@ -12,6 +12,9 @@ int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_pr
                  int* status, double* obj, int* iters, void* ws, size_t ws_bytes, hipStream_t stream,
                  double* trace = nullptr);
 
+int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                     double* w_out, int* status, double* obj, int* iters, hipStream_t stream);
+
 int backtest_run_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int step0, int n_steps,
                         const float* yhat, const float* realized, int n_real, double* weights, double* value,
                         double* hist, double* target, int* status, double* obj, hipStream_t stream);

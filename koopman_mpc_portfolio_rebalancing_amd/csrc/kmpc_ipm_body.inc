@@ -2,7 +2,8 @@
 // ipm_kernel (kmpc_solve_kernel.h) and by the path-persistent backtest kernel (kmpc_solve_c3.hip,
 // once per step). An include rather than a function: ipm_kernel's instruction stream stays exactly
 // what it was (a call boundary, even inlined, reshuffles this kernel's register allocation).
-// Names in scope at the include: HM, MAXT, EXACT, FL, CS, QL, GL, PH (template parameters), Real,
+// Names in scope at the include: HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX (template parameters; BOX
+// a constant false where the kernel has no box form), Real,
 // NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window: w_prev, outputs, warm record),
 // yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h).
     if constexpr (PH == 3) {   // the retry pass: only windows whose warm start did not end optimal
@@ -16,8 +17,9 @@
     // only for 128-thread blocks), so the reductions' per-wave slot loops need no run-time guards
     const int nw = GL < 64 ? 1 : (MAXT <= 128 ? NWM : (int)(blockDim.x / WAVE));
     Reducer<HM, NWM, GL, Real> R(sh, nw);
-    Thread<HM, MAXT, FL, CS, QL, GL, Real> T;
+    Thread<HM, MAXT, FL, CS, QL, GL, Real, BOX> T;
     T.bind_cold();
+    if constexpr (BOX) T.u = Real(args.max_weight);
     T.H = EXACT ? HM : args.H;
     T.N = args.N;
     T.i = gvt<GL>();
@@ -182,6 +184,9 @@
                 for (int t = 0; t < HM; ++t) {
                     const Real b0 = T.hw ? fmax(T.wpi, Real(0.0)) : T.wpi;
                     T.w[t] = (T.act && t < H) ? Real(0.5) * b0 + Real(0.5) / N : Real(0.0);
+                    // box case: strictly inside 0 < w < u (N u > 1, so 1 / N < u)
+                    if constexpr (BOX)
+                        if (T.act && t < H) T.w[t] = fmin(T.w[t], Real(0.5) * (T.u + Real(1.0) / N));
                 }
                 Real ss0[HM];
 #pragma unroll
@@ -192,6 +197,7 @@
                     ss0[t] = T.s[t];
                     T.l1[t] = (on && T.hw) ? Real(KMPC_INIT_MULT) : Real(0.0);
                     T.l2[t] = T.l3[t] = (on && T.hs) ? Real(KMPC_INIT_MULT) : Real(0.0);
+                    if constexpr (BOX) T.l5[t] = on ? Real(KMPC_INIT_MULT) : Real(0.0);
                 }
                 const Real st0 = R.own1(ss0);
                 if (gvt<GL>() < HM) {
@@ -203,7 +209,7 @@
                 }
             }
             __syncthreads();
-            const int ncon = (T.hw ? H * N : 0) + (T.hs ? 2 * H * N : 0) + (T.ht ? H : 0);
+            const int ncon = (T.hw ? H * N : 0) + (T.hs ? 2 * H * N : 0) + (T.ht ? H : 0) + (BOX ? H * N : 0);
             const Real inv_ncon = Real(1.0) / (ncon > 0 ? ncon : 1);
             Real best = huge_of<Real>(), min_pr = huge_of<Real>();
             Real last_mu = huge_of<Real>();   // PH = 1: stagnation test
@@ -261,6 +267,7 @@
                         dual_residual<HM, NWM>(T, sh, t, rdw, rds);
                         mu_l += (T.hw ? T.w[t] * T.l1[t] : Real(0.0)) +
                                 (T.hs ? (T.s[t] - d) * T.l2[t] + (T.s[t] + d) * T.l3[t] : Real(0.0));
+                        if constexpr (BOX) mu_l += T.xl5(t);
                         rd = fmax(rd, fmax(fabs(rdw), fabs(rds)));
                     }
                 }
@@ -316,6 +323,7 @@
                     T.rc1.set(t, r1);
                     T.rc2.set(t, r2);
                     T.rc3.set(t, r3);
+                    if constexpr (BOX) T.rc5.set(t, t < H ? T.xl5(t) : Real(0.0));
                 }
 
                 // ---- predictor (pass 0) and corrector (pass 1) share one Newton body ----
@@ -372,6 +380,11 @@
                             T.rc2.set(t, r2);
                             T.rc3.set(t, r3);
                         }
+                        if constexpr (BOX) {   // (u - w) l5 + (-dw_aff) dl5_aff - sigma mu
+                            Real r5 = Real(0.0);
+                            if (t < H) r5 = T.rc5[t] - T.dw[t] * T.dual_dir5(t) - smu;
+                            T.rc5.set(t, r5);
+                        }
                     }
                     if (gvt<GL>() < HM && T.ht && (int)gvt<GL>() < H) {
                         const int t = gvt<GL>();
@@ -393,6 +406,13 @@
                             T.l2[t] += step * DL2[t];
                             T.l3[t] += step * DL3[t];
                         }
+                    }
+                    if constexpr (BOX) {
+                        Real DL5[HM];
+                        T.dual_dirs5_all(DL5);
+#pragma unroll
+                        for (int t = 0; t < HM; ++t)
+                            if (t < H) T.l5[t] += step * DL5[t];
                     }
                 }
 #pragma unroll

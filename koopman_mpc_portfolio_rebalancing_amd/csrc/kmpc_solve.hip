@@ -400,6 +400,40 @@ int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_pr
     return KMPC_ERR_UNSUPPORTED;   // H > 10: the large-window kernel
 }
 
+// kmpc_solve_box: the program of kmpc_solve with a per-asset position limit w <= max_weight, in the
+// box case of the generic float64 register kernels (launch_ipm_box) at every batch size: no
+// presolve (the capped simplex has no closed form here), no packing, no mixed pair, no workspace.
+// The caller (kmpc_capi.hip) has checked the shape and the limit: no short, 1 / N < max_weight < 1,
+// N <= 256, H <= 10.
+int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                     double* w_out, int* status, double* obj, int* iters, hipStream_t stream) {
+    if (d->B > LAUNCH_MAX_B) {   // equal launches, as solve_launch
+        const int nch = (int)(((size_t)d->B + LAUNCH_MAX_B - 1) / LAUNCH_MAX_B);
+        const int per = (int)(((size_t)d->B + nch - 1) / nch);
+        const size_t HN = (size_t)d->H * d->N, wo = d->return_full_W ? HN : (size_t)d->N;
+        kmpc_solve_desc c = *d;
+        for (int b0 = 0; b0 < d->B; b0 += per) {
+            c.B = d->B - b0 < per ? d->B - b0 : per;
+            const int rc = solve_box_launch(&c, max_weight, yhat + (size_t)b0 * HN, w_prev + (size_t)b0 * d->N,
+                                            w_out + (size_t)b0 * wo, status + b0, obj + b0,
+                                            iters ? iters + b0 : nullptr, stream);
+            if (rc != KMPC_OK) return rc;
+        }
+        return KMPC_OK;
+    }
+    SolveArgs a = make_args(d);
+    a.yhat = yhat; a.wp = w_prev; a.wout = w_out; a.status = status; a.obj = obj; a.iters = iters;
+    a.trace = nullptr;
+    a.max_weight = max_weight;   // (shares mu_handoff's slot: the box kernels have no float32 phase)
+    if (a.B == 0) return KMPC_OK;
+#ifndef KMPC_DEV_ONLY_H10
+    if (a.H <= 2) return launch_ipm_box<2>(a, stream);
+    if (a.H <= 5) return launch_ipm_box<5>(a, stream);
+    if (a.H <= 10) return launch_ipm_box<10>(a, stream);
+#endif
+    return KMPC_ERR_UNSUPPORTED;
+}
+
 // kmpc_backtest_run: a path-persistent kernel exists for the shapes whose per-step batch of P
 // windows kmpc_solve sends to a float64 constant-case register kernel (case 7: no short, cost and
 // cap; H = 10 or 5 with 32 < N <= 256, one window per workgroup; and the packed N <= 32 kernels

@@ -20,7 +20,13 @@ struct SolveArgs {
     // mixed precision (kmpc_solve_kernel.h, PH = 1 / 2): one warm record per window, or null
     float* warm;
     size_t warm_floats;   // floats per window in warm (mixed_warm_floats)
-    double mu_handoff;   // the float32 phase hands its iterate over at mu <= mu_handoff
+    // the float32 phase hands its iterate over at mu <= mu_handoff. The box kernels (kmpc_solve_box:
+    // float64 only, no float32 phase) read the per-asset position limit from the same slot, so the
+    // struct — the kernel argument of every solve kernel — keeps its size and offsets.
+    union {
+        double mu_handoff;
+        double max_weight;
+    };
 };
 
 // A period whose gross returns R = np.exp(yhat) sum below this is solved on R / sum(R) (the same
@@ -43,6 +49,9 @@ constexpr int QL_CS = 104;     // cold-array stride of the 128-thread QL variant
 // ipm_kernel launchers, one translation unit per compile-time horizon bound HM (kmpc_solve_h*.hip)
 template <int HM>
 int launch_ipm(const SolveArgs& a, hipStream_t stream);
+// ... of the box case (a.max_weight: per-asset position limit; kmpc_solve_hbox*.hip)
+template <int HM>
+int launch_ipm_box(const SolveArgs& a, hipStream_t stream);
 // large-window kernel (kmpc_solve_big.hip): workspace it needs, and the launch
 size_t big_ws_bytes(const SolveArgs& a);
 int big_launch(const SolveArgs& a, void* ws, size_t ws_size, hipStream_t stream);

@@ -1,0 +1,7 @@
+// kmpc_solve_hbox2.hip — box-case ipm_kernel instantiations (per-asset position limit,
+// kmpc_solve_box) for horizons H <= 2 (see kmpc_solve_kernel.h: launch_ipm_box).
+#include "kmpc_solve_kernel.h"
+
+namespace kmpc {
+template int launch_ipm_box<2>(const SolveArgs& a, hipStream_t stream);
+}  // namespace kmpc

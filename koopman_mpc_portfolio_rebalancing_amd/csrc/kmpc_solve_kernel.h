@@ -606,7 +606,8 @@ struct Cold<Real, HM, CS, true, GL> {
     __device__ __forceinline__ void set(int t, Real x) { base()[(k * HM + t) * CS + lane()] = x; }
 };
 // cold arrays: rc1, rc2, rc3, iw, iz2, iz3 (+ iDd, Lr of the per-asset LDL^T when QL)
-__host__ __device__ constexpr int n_cold(bool ql) { return ql ? 8 : 6; }
+// (+ iu, rc5 of the box case, BOX: the position limit's slack reciprocal and target)
+__host__ __device__ constexpr int n_cold(bool ql, bool box = false) { return (ql ? 8 : 6) + (box ? 2 : 0); }
 // cold arrays go to LDS when they fit next to the static LDS (G, its transpose, reduction slots)
 // within one CU's 160 KB; otherwise (HM = 21, or 1024-thread blocks) they stay in registers.
 // Packed kernels of the no-short-only case (FL = 1, no turnover terms: ~24 dwords spilled with the
@@ -620,14 +621,41 @@ __host__ __device__ constexpr int n_cold(bool ql) { return ql ? 8 : 6; }
 #ifndef KMPC_F32_COLD_REG
 #define KMPC_F32_COLD_REG 1
 #endif
-template <int HM, int MAXT, int CS, bool QL, int GL = 64, int FL = -1, class Real = double>
+// BOX: all n_cold(QL, true) arrays, the box case's two included. Where these do not fit (HM = 10
+// at a 256-lane stride), or would halve the workgroups resident on a CU (HM = 10 with 128 threads
+// at a 128-lane stride, HM = 5 with 256: two windows per CU -> one), the box kernel keeps its own
+// two in registers and the others in LDS as the plain kernel does (Thread's BoxState). Measured,
+// 65,536 / 32,768 / 16,384 windows, all in LDS -> this rule: N = 120, H = 10 135.0 -> 93.0 ms,
+// N = 200, H = 5 47.0 -> 32.1 ms; where LDS costs a quarter of the workgroups the spills cost
+// more (registers at N = 10 / 50 / 100, H = 5: 16.5 -> 18.5, 20.0 -> 22.4, 21.8 -> 23.9 ms), so
+// those keep LDS (profiles/box_resource_usage.md).
+#ifndef KMPC_BOX_COLD_MODE   // 0 = dev A/B: in LDS wherever they fit
+#define KMPC_BOX_COLD_MODE 1
+#endif
+template <int HM, int NWM, class Real>
+struct Shared;
+// workgroups of MAXT threads resident on one CU with ncold cold arrays in LDS: the smaller of the
+// wave limit (four SIMDs at the kernel's waves per SIMD) and the LDS limit (160 KB)
+template <int HM, int MAXT, int CS, class Real>
+constexpr int resident_blocks(int ncold) {
+    const int by_waves = max_i(1, 4 * (HM <= KMPC_WPE2_HM ? 2 : 1) / (MAXT / 64));
+    const int by_lds = (int)((160 * 1024) / (sizeof(Shared<HM, MAXT / 64, Real>) + sizeof(Real) * ncold * HM * CS));
+    return by_lds < by_waves ? by_lds : by_waves;
+}
+template <int HM, int MAXT, int CS, bool QL, int GL = 64, int FL = -1, class Real = double, bool BOX = false>
 constexpr bool cold_in_lds() {
     if (sizeof(Real) == 4 && KMPC_F32_COLD_REG) return false;
     if (GL < 64 && (KMPC_PACKED_COLD_REG || FL == 1)) return false;
-    return MAXT <= 256 && (n_cold(QL) * HM * CS + 9 * HM * HM) * 8 + 16 * 1024 <= 160 * 1024;
+    if constexpr (BOX && KMPC_BOX_COLD_MODE)
+        if (2 * resident_blocks<HM, MAXT, CS, Real>(n_cold(QL, true)) <= resident_blocks<HM, MAXT, CS, Real>(n_cold(QL)))
+            return false;
+    return MAXT <= 256 && (n_cold(QL, BOX) * HM * CS + 9 * HM * HM) * 8 + 16 * 1024 <= 160 * 1024;
 }
-template <int HM, int MAXT, int CS, bool QL, int GL = 64, int FL = -1, class Real = double>
-constexpr size_t cold_bytes() { return cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real>() ? sizeof(Real) * n_cold(QL) * HM * CS : 0; }
+template <int HM, int MAXT, int CS, bool QL, int GL = 64, int FL = -1, class Real = double, bool BOX = false>
+constexpr size_t cold_bytes() {
+    if (BOX && cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real, true>()) return sizeof(Real) * n_cold(QL, true) * HM * CS;
+    return cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real>() ? sizeof(Real) * n_cold(QL) * HM * CS : 0;
+}
 
 // ---- shared state -------------------------------------------------------------------------------
 
@@ -673,14 +701,28 @@ struct Case<-1> {
 };
 __host__ __device__ constexpr int case_of(bool hw, bool hs, bool ht) { return (hw ? 1 : 0) | (hs ? 2 : 0) | (ht ? 4 : 0); }
 
-template <int HM, int MAXT, int FL = -1, int CS = MAXT, bool QL = false, int GL = 64, class Real = double>
-struct Thread : Case<FL> {
+// State of the box case (BOX: the per-asset position limit w <= u, one more barrier on w with slack
+// u - w taken from the iterate): the multiplier l5, and two cold arrays, the slack
+// reciprocal iu = 1 / (u - w) and the complementarity target rc5. Empty without the box.
+template <class Real, int HM, int CS, bool LB, int GL, bool BOX>
+struct BoxState {};
+template <class Real, int HM, int CS, bool LB, int GL>
+struct BoxState<Real, HM, CS, LB, GL, true> {
+    Real u;          // the limit
+    Real l5[HM];     // multiplier of u - w >= 0
+    Cold<Real, HM, CS, LB, GL> iu, rc5;
+};
+
+template <int HM, int MAXT, int FL = -1, int CS = MAXT, bool QL = false, int GL = 64, class Real = double, bool BOX = false>
+struct Thread : Case<FL>, BoxState<Real, HM, CS, cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real, true>(), GL, BOX> {
+    static_assert(!(BOX && QL), "the box case keeps the per-asset LDL^T arrays in registers");
     using Case<FL>::hw;
     using Case<FL>::hs;
     using Case<FL>::ht;
     using real_t = Real;
     static constexpr int GLN = GL;   // lanes per window (lane groups)
     static constexpr int CSV = CS;   // cold-array stride (slots per row)
+    static constexpr bool BOXV = BOX;   // the box case (position limit w <= u)
     static constexpr bool L = cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real>();
     int H, N, i;
     // act: this lane's asset exists (i < N). Inactive lanes keep a zero iterate (w = s = l = m = 0,
@@ -704,6 +746,7 @@ struct Thread : Case<FL> {
     __device__ __forceinline__ void bind_cold() {
         rc1.bind(0); rc2.bind(1); rc3.bind(2); iw.bind(3); iz2.bind(4); iz3.bind(5);
         iDd.bind(6); Lr.bind(7);
+        if constexpr (BOX) { this->iu.bind(6); this->rc5.bind(7); }   // (no QL box form: slots 6, 7 are free)
     }
 
     __device__ __forceinline__ Real wprev(int t) const { return t ? w[t - 1] : wpi; }
@@ -762,6 +805,29 @@ struct Thread : Case<FL> {
                     dl3[t] = hs ? (-c[2][j] - l3[t] * (ds[t] + dd)) * c[5][j] : Real(0.0);
                 }
             }
+        }
+    }
+
+    // box case: the limit's target (u - w) l5 of period t, and its multiplier along the current
+    // direction (slack direction -dw): dl5 = (-rc5 + l5 dw) / (u - w)
+    __device__ __forceinline__ Real xl5(int t) const {
+        if constexpr (BOX) return (this->u - w[t]) * this->l5[t];
+        else return Real(0.0);
+    }
+    __device__ __forceinline__ Real dual_dir5(int t) const {
+        if constexpr (BOX) return (-this->rc5[t] + this->l5[t] * dw[t]) * this->iu[t];
+        else return Real(0.0);
+    }
+    __device__ __forceinline__ void dual_dirs5_all(Real (&dl5)[HM]) const {
+        Real c[2][HM];
+#pragma unroll
+        for (int t = 0; t < HM; ++t) {
+            if constexpr (BOX) { c[0][t] = this->rc5[t]; c[1][t] = this->iu[t]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < HM; ++t) {
+            if constexpr (BOX) dl5[t] = (-c[0][t] + this->l5[t] * dw[t]) * c[1][t];
         }
     }
 
@@ -1070,7 +1136,8 @@ __device__ __forceinline__ void dual_residual(const TH& T, const Shared<HM, NWM,
                                               Real& rdw, Real& rds) {
     const Real eta = T.l3[t] - T.l2[t];
     const Real etan = (t + 1 < HM && t + 1 < T.H) ? T.l3[t + 1] - T.l2[t + 1] : Real(0.0);
-    rdw = -T.m[t] * sh.iden[t] * T.isig - (T.l1[t] + eta - etan) + sh.nu[t];
+    if constexpr (TH::BOXV) rdw = -T.m[t] * sh.iden[t] * T.isig - ((T.l1[t] - T.l5[t]) + eta - etan) + sh.nu[t];
+    else rdw = -T.m[t] * sh.iden[t] * T.isig - (T.l1[t] + eta - etan) + sh.nu[t];
     rds = T.hs ? T.c - (T.l2[t] + T.l3[t] - sh.l4[t]) : Real(0.0);
 }
 
@@ -1096,6 +1163,7 @@ __device__ __forceinline__ void lsolve(const TH& T, Shared<HM, NWM, typename TH:
         Real p1 = Real(0.0), p2 = Real(0.0), p3 = Real(0.0), pn = Real(0.0);
         if (with_c) {
             p1 = T.hw ? -T.rc1[t] * T.iw[t] : Real(0.0);
+            if constexpr (TH::BOXV) p1 += T.rc5[t] * T.iu[t];
             p2 = T.hs ? -T.rc2[t] * T.iz2[t] : Real(0.0);
             p3 = T.hs ? -T.rc3[t] * T.iz3[t] : Real(0.0);
             if (t + 1 < HM && T.hs) pn = -T.rc3[t + 1] * T.iz3[t + 1] + T.rc2[t + 1] * T.iz2[t + 1];
@@ -1269,6 +1337,8 @@ __device__ __forceinline__ void newton(TH& T, Shared<HM, NWM, typename TH::real_
             if (n_refine > 0)   // ||b||_inf only matters when the solve may be refined
                 bn = fmax(bn, fmax(fmax(fabs(rdw), fabs(rds)),
                                    fmax(fabs(T.rc1[t]), fmax(fabs(T.rc2[t]), fabs(T.rc3[t])))));
+            if constexpr (TH::BOXV)
+                if (n_refine > 0) bn = fmax(bn, fabs(T.rc5[t]));
         }
     }
     if (!T.act) bn = Real(0.0);
@@ -1323,6 +1393,7 @@ __device__ __forceinline__ void newton(TH& T, Shared<HM, NWM, typename TH::real_
         for (int t = HM - 1; t >= 0; --t) {
             Real dl1, dl2, dl3;
             T.dual_dirs(t, dl1, dl2, dl3);
+            if constexpr (TH::BOXV) dl1 -= T.dual_dir5(t);   // (the w row carries l1 - l5)
             if (t < H) {   // (inactive lanes' rows: masked in lsolve and in rn below)
                 Real rdw, rds;
                 dual_residual<HM, NWM>(T, sh, t, rdw, rds);
@@ -1380,6 +1451,8 @@ __device__ __forceinline__ Real max_step(const TH& T, Shared<HM, NWM, typename T
     c1 = c2 = Real(0.0);
     Real DL1[HM], DL2[HM], DL3[HM];
     T.dual_dirs_all(DL1, DL2, DL3);
+    Real DL5[TH::BOXV ? HM : 1];
+    if constexpr (TH::BOXV) T.dual_dirs5_all(DL5);
     // primal bounds (w, s -+ d) through the slack reciprocals factor() stored for this iterate:
     // the largest -dx / x, inverted once, instead of one reciprocal per ratio
     Real qx = Real(0.0);
@@ -1395,6 +1468,13 @@ __device__ __forceinline__ Real max_step(const TH& T, Shared<HM, NWM, typename T
                 a = to_bound(T.l1[t], dl1, a);
                 c1 += T.w[t] * dl1 + T.l1[t] * T.dw[t];
                 c2 += T.dw[t] * dl1;
+            }
+            if constexpr (TH::BOXV) {   // u - w > 0 (direction -dw) and l5 > 0
+                const Real dl5 = DL5[t];
+                qx = fmax(qx, T.dw[t] * T.iu[t]);
+                a = to_bound(T.l5[t], dl5, a);
+                c1 += (T.u - T.w[t]) * dl5 - T.l5[t] * T.dw[t];
+                c2 -= T.dw[t] * dl5;
             }
             if (T.hs) {
                 const Real x2 = T.s[t] - d, dx2 = T.ds[t] - dd, x3 = T.s[t] + d, dx3 = T.ds[t] + dd;
@@ -1483,6 +1563,11 @@ __device__ __forceinline__ bool factor(TH& T, Shared<HM, NWM, typename TH::real_
         if (T.act && t < H) {
             const Real d = T.w[t] - T.wprev(t);
             if (T.hw) { iw = rcp_nr(T.w[t]); W1[t] = T.l1[t] * iw; }
+            if constexpr (TH::BOXV) {
+                const Real iu = rcp_nr(T.u - T.w[t]);
+                W1[t] += T.l5[t] * iu;
+                T.iu.set(t, iu);
+            }
             if (T.hs) {
                 iz2 = rcp_nr(T.s[t] - d);
                 iz3 = rcp_nr(T.s[t] + d);
@@ -1496,6 +1581,8 @@ __device__ __forceinline__ bool factor(TH& T, Shared<HM, NWM, typename TH::real_
         T.iw.set(t, iw);
         T.iz2.set(t, iz2);
         T.iz3.set(t, iz3);
+        if constexpr (TH::BOXV)
+            if (!(T.act && t < H)) T.iu.set(t, Real(0.0));
     }
     const Real st_own = R.own1(sp);
     if (gvt<TH::GLN>() < HM) {
@@ -1823,9 +1910,15 @@ __device__ __forceinline__ Real record_best(const TH& T, Reducer<HM, NWM, TH::GL
 // z4, l4, nu) goes to the window's record in args.warm and the kernel exits (no outputs); a window
 // it cannot hand over (special cases, a float breakdown) is marked cold; 2 = the float64 solve,
 // started from the window's record when it is warm (from the usual initial point when cold).
-template <int HM, int MAXT, bool EXACT, int FL = -1, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0>
+// BOX: the box case, a per-asset position limit w <= args.max_weight (kmpc_solve_box; float64,
+// whole-wave windows, the generic constraint case only).
+// The window body (kmpc_ipm_body.inc) reads BOX by name: the kernels that include it without a box
+// form (the mixed, path-persistent and sweep kernels) see this constant, ipm_kernel its own parameter.
+constexpr bool BOX = false;
+template <int HM, int MAXT, bool EXACT, int FL = -1, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0, bool BOX = false>
 __global__ void __launch_bounds__(MAXT)
 __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM ? 2 : 1)))) ipm_kernel(SolveArgs args) {
+    static_assert(!BOX || (FL == -1 && GL == 64 && PH == 0 && !QL), "box kernels: generic float64, whole waves");
     static_assert(3 * HM <= GL, "Schur system must fit one lane group");
     static_assert(GL == 64 || MAXT == 64, "lane groups pack one-wave blocks");
     using Real = std::conditional_t<PH == 1, float, double>;
@@ -1835,7 +1928,7 @@ __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM 
     // cover the real Shared, and static + dynamic LDS must fit one CU
     static_assert(!cold_in_lds<HM, MAXT, CS, QL, GL, FL, Real>() ||
                   sizeof(Shared<HM, NWM, Real>) * WPB <= 9 * HM * HM * 8 + 16 * 1024, "cold_in_lds() LDS estimate");
-    static_assert(sizeof(Shared<HM, NWM, Real>) * WPB + cold_bytes<HM, MAXT, CS, QL, GL, FL, Real>() <= 160 * 1024,
+    static_assert(sizeof(Shared<HM, NWM, Real>) * WPB + cold_bytes<HM, MAXT, CS, QL, GL, FL, Real, BOX>() <= 160 * 1024,
                   "LDS of one workgroup");
     __shared__ Shared<HM, NWM, Real> shv[WPB];
     auto& sh = shv[grp<GL>()];
@@ -1845,11 +1938,11 @@ __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM 
 #include "kmpc_ipm_body.inc"
 }
 
-template <int HM, int MAXT, bool EXACT, int FL, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0>
+template <int HM, int MAXT, bool EXACT, int FL, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0, bool BOX = false>
 int launch_one(const SolveArgs& a, int nt, hipStream_t stream) {
-    const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, std::conditional_t<PH == 1, float, double>>();
+    const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, std::conditional_t<PH == 1, float, double>, BOX>();
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;
-    hipLaunchKernelGGL((ipm_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, PH>), dim3((a.B + WPB - 1) / WPB), dim3(nt), lds, stream, a);
+    hipLaunchKernelGGL((ipm_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX>), dim3((a.B + WPB - 1) / WPB), dim3(nt), lds, stream, a);
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
@@ -1871,6 +1964,30 @@ int launch_ipm(const SolveArgs& a, hipStream_t stream) {
     if (nt <= 256) return exact ? launch_one<HM, 256, true, -1>(a, nt, stream) : launch_one<HM, 256, false, -1>(a, nt, stream);
     // past 256 assets a window's state does not fit the registers of one block: kmpc_solve_big.h
     return KMPC_ERR_UNSUPPORTED;
+}
+
+// Box launcher (kmpc_solve_box: a.max_weight = the per-asset position limit, no short): the generic
+// float64 kernel's box case, one workgroup of 64 ceil(N / 64) threads per window, H <= HM read at
+// run time. Three kernels per horizon bound (kmpc_solve_hbox*.hip), and the 104-lane-stride one
+// below; no packed, constant-case, QL or mixed forms.
+// ... plus, at H <= 10, a 128-thread kernel with the cold arrays at the C3 kernel's 104-lane stride
+// for N < 104 (BASELINE configs[2]'s shape): all eight in LDS and still two windows per CU —
+// 65,536 C3 windows 166.4 -> 132.0 ms against the 128-lane stride with the box arrays in registers
+// (242.9 ms with all eight at the 128-lane stride, one window per CU). 0 = dev A/B.
+#ifndef KMPC_BOX_QLCS
+#define KMPC_BOX_QLCS 1
+#endif
+template <int HM>
+int launch_ipm_box(const SolveArgs& a, hipStream_t stream) {
+    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
+    if (a.H > HM || nt > 256) return KMPC_ERR_UNSUPPORTED;
+#if KMPC_BOX_QLCS
+    if constexpr (HM == 10)
+        if (nt == 128 && a.N < QL_CS) return launch_one<HM, 128, false, -1, QL_CS, false, 64, 0, true>(a, nt, stream);
+#endif
+    if (nt <= 64) return launch_one<HM, 64, false, -1, 64, false, 64, 0, true>(a, nt, stream);
+    if (nt <= 128) return launch_one<HM, 128, false, -1, 128, false, 64, 0, true>(a, nt, stream);
+    return launch_one<HM, 256, false, -1, 256, false, 64, 0, true>(a, nt, stream);
 }
 
 // Constant-case launcher (H == HM, N <= 128; case 7 up to 256): the constraint case is a template argument, so every

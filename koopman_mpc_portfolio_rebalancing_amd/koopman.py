@@ -276,12 +276,22 @@ class DeviceKoopman:
                keep_yhat: bool = False, return_full: bool = False, with_iters: bool = False):
         """Fused window (kmpc_window): obs [B, obs], w_prev [B, N] -> (W0 or W, status, value[, yhat]
         [, iters]) — iters [B] int32 interior-point iterations when with_iters."""
-        from .mpc import _solve_desc
+        from .mpc import _box_limit, _solve_desc, solve_mpc_log_utility_batched
         _lib.require_gpu(obs)
         x = obs.to(self.device, torch.float32).contiguous()
         self._check_obs(x)
         B = x.shape[0]
         H = int(mpc_config.horizon)
+        if _box_limit(mpc_config, n_assets):
+            # a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it, so no fused
+            # kmpc_window — kmpc_rollout, then kmpc_solve_box on the same stream
+            if w_prev.shape != (B, int(n_assets)):
+                raise ValueError(f"w_prev must be [{B}, {int(n_assets)}], got {tuple(w_prev.shape)}")
+            with torch.cuda.device(self.device):
+                yh = self.rollout(x, mean, std, H, n_assets)
+                res = solve_mpc_log_utility_batched(w_prev.to(self.device), yh, mpc_config, return_full=return_full,
+                                                    with_iters=with_iters)
+            return res[:3] + ((yh,) if keep_yhat else ()) + ((res[3],) if with_iters else ())
         wp = w_prev.to(self.device, torch.float64).contiguous()
         if wp.shape != (B, int(n_assets)):
             raise ValueError(f"w_prev must be [{B}, {int(n_assets)}], got {tuple(wp.shape)}")

@@ -37,6 +37,25 @@ class MPCConfig:
     solver_path: int = 0  # kmpc_solve_desc.path: 0 by shape, 1 register IPM (no presolve), 2 large-window IPM, 3 register IPM without lane-group packing
     precision: str = "auto"  # kmpc_solve_desc.precision: "mixed" (float32 warm-start phase + float64 finish where available), "f64", or "auto" (mixed from 2,048 windows per call, else f64)
     mu_handoff: float = 0.0  # float32 -> float64 handoff at mu <= mu_handoff (0 -> kernel default 3e-5)
+    max_weight: float = 0.0  # per-asset position limit w <= max_weight of the log-utility solve (kmpc_solve_box); 0 or >= 1: none
+
+
+def _box_limit(config: MPCConfig, N: int) -> float:
+    """The active per-asset position limit of `config` for N assets, or 0.0 when it has none
+    (max_weight 0, or >= 1: the simplex already bounds every weight by 1). kmpc_solve_desc cannot
+    carry the limit, so every caller that turns an MPCConfig into a solve goes through here and
+    then through kmpc_solve_box. Raises ValueError where no program exists: a negative or NaN
+    limit, N * max_weight <= 1 (empty set, or the single point 1/N), or together with allow_short."""
+    u = float(getattr(config, "max_weight", 0.0))
+    if u != u or u < 0.0:
+        raise ValueError(f"max_weight must be >= 0 (got {u})")
+    if u == 0.0 or u >= 1.0:
+        return 0.0
+    if bool(config.allow_short):
+        raise ValueError("max_weight is a long-only position limit: not available with allow_short")
+    if int(N) * u <= 1.0:
+        raise ValueError(f"max_weight = {u} leaves no room with N = {int(N)} assets (N * max_weight must exceed 1)")
+    return u
 
 
 def _solve_desc(B: int, N: int, H: int, config: MPCConfig, full: bool) -> _lib.SolveDesc:
@@ -105,6 +124,14 @@ def solve_mpc_log_utility_batched(
     iters = torch.empty(B, dtype=torch.int32, device=y.device)
     d = _solve_desc(B, N, H, config, return_full)
     L = _lib.load()
+    u = _box_limit(config, N)
+    if u:   # the position limit: the box case of the float64 register kernels (no workspace)
+        with torch.cuda.device(y.device):
+            rc = L.kmpc_solve_box(ctypes.byref(d), u, y.data_ptr(), wp.data_ptr(), W.data_ptr(),
+                                  status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                                  _lib.stream_handle(y.device))
+        _lib.check(rc)
+        return (W, status, value, iters) if with_iters else (W, status, value)
     with torch.cuda.device(y.device):
         nws = int(L.kmpc_workspace_bytes(None, ctypes.byref(d)))
         ws = _workspace(y.device, nws) if nws else None

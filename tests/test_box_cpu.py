@@ -1,0 +1,154 @@
+"""The per-asset position limit (MPCConfig.max_weight, kmpc_solve_box) without a GPU: the symbol
+and the unchanged ABI version, every return-code rule of the C function (decided before any
+launch), the Python helper, and the goldens pinned by an LP certificate and the dense reference."""
+import ctypes
+import glob
+import os
+import re
+
+import numpy as np
+import pytest
+
+import box_ref
+import koopman_mpc_portfolio_rebalancing_amd as pkg
+from koopman_mpc_portfolio_rebalancing_amd import _lib
+from koopman_mpc_portfolio_rebalancing_amd.mpc import MPCConfig, _box_limit
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+BOX_FILES = sorted(glob.glob(os.path.join(GOLD, "box_N*_H*.npz")))
+OK, INVALID, UNSUPPORTED, WORKSPACE = 0, -1, -2, -3
+
+
+def test_symbol_and_version():
+    lib = _lib.load()
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "kmpc.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+kmpc_solve_box\s*\(", hdr)
+    assert "kmpc_solve_box" in _lib.EXPORTED_SYMBOLS
+    assert hasattr(lib, "kmpc_solve_box")
+    assert _lib.ABI_VERSION == "0.7.0" == pkg.__version__
+    assert lib.kmpc_version().decode() == "kmpc 0.7.0 (gfx950)"
+    assert MPCConfig().max_weight == 0.0
+
+
+def _desc(B=0, N=10, H=5, c=1e-3, tau=0.2, short=0, path=0, precision=0):
+    d = _lib.SolveDesc()
+    d.B, d.N, d.H, d.cost_coeff, d.max_turnover, d.allow_short = B, N, H, c, tau, short
+    d.path, d.precision = path, precision
+    return d
+
+
+def _box(d, u):
+    return _lib.load().kmpc_solve_box(ctypes.byref(d), u, None, None, None, None, None, None, None)
+
+
+def test_return_codes_need_no_gpu():
+    # check_solve applies as for kmpc_solve
+    assert _lib.load().kmpc_solve_box(None, 0.5, None, None, None, None, None, None, None) == INVALID
+    assert _box(_desc(H=0), 0.5) == INVALID
+    assert _box(_desc(c=-1e-3), 0.5) == INVALID
+    assert _box(_desc(path=7), 0.5) == INVALID
+    assert _box(_desc(H=40), 0.5) == UNSUPPORTED
+    # the limit itself
+    for u in (float("nan"), 0.0, -0.1, -float("inf")):
+        assert _box(_desc(), u) == INVALID
+    # N u <= 1: empty set, or the single point 1/N
+    assert _box(_desc(N=10), 0.1) == INVALID
+    assert _box(_desc(N=10), 0.05) == INVALID
+    assert _box(_desc(N=4), 0.25) == INVALID
+    assert _box(_desc(N=256), 1.0 / 256) == INVALID
+    # an inactive bound is kmpc_solve without a workspace
+    assert _box(_desc(), 1.0) == OK
+    assert _box(_desc(), 7.0) == OK
+    assert _box(_desc(B=3), 1.0) == INVALID                       # kmpc_solve's null-array check
+    assert _box(_desc(N=500, H=10), 1.0) == OK                    # (B = 0: nothing to solve)
+    # (non-null arrays, never read: the workspace rule is decided before any launch)
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    box_p = lambda d, u: _lib.load().kmpc_solve_box(ctypes.byref(d), u, p, p, p, p, p, None, None)
+    assert box_p(_desc(B=4, N=500, H=10), 1.0) == WORKSPACE       # the large-window kernel needs one
+    assert box_p(_desc(B=4, N=100, H=10, precision=2), 1.0) == WORKSPACE   # ... as does the mixed pair
+    # unsupported combinations
+    assert _box(_desc(short=1), 0.5) == UNSUPPORTED
+    assert _box(_desc(short=1), 1.0) == UNSUPPORTED
+    assert _box(_desc(N=257), 0.5) == UNSUPPORTED
+    assert _box(_desc(N=300), 0.5) == UNSUPPORTED
+    assert _box(_desc(H=11), 0.5) == UNSUPPORTED
+    assert _box(_desc(H=12), 0.5) == UNSUPPORTED
+    assert _box(_desc(path=_lib.PATH_LARGE), 0.5) == UNSUPPORTED
+    assert _box(_desc(precision=_lib.PRECISION_MIXED), 0.5) == UNSUPPORTED
+    # the rules come before the B == 0 return and before the null-array check
+    assert _box(_desc(B=0, N=300), 0.5) == UNSUPPORTED
+    assert _box(_desc(B=5), 0.5) == INVALID                       # null arrays
+    # every supported shape probe
+    for N, H in ((2, 1), (3, 2), (10, 5), (13, 4), (64, 10), (65, 6), (100, 10), (128, 5), (129, 2), (200, 10),
+                 (256, 5), (256, 10)):
+        for prec in (_lib.PRECISION_AUTO, _lib.PRECISION_F64):
+            for path in (_lib.PATH_AUTO, _lib.PATH_REGISTER, _lib.PATH_REGISTER_UNPACKED):
+                assert _box(_desc(N=N, H=H, precision=prec, path=path), 0.6) == OK, (N, H, prec, path)
+    assert _box(_desc(c=0.0, tau=0.0, N=30), 0.1) == OK
+    assert _box(_desc(tau=-1.0), 0.5) == OK
+
+
+def test_box_limit_helper():
+    for u in (0, 0.0, 1, 1.0, 2.5):
+        assert _box_limit(MPCConfig(max_weight=u), 10) == 0.0
+    assert _box_limit(MPCConfig(max_weight=1.0, allow_short=True), 10) == 0.0
+    assert _box_limit(MPCConfig(max_weight=0.25), 10) == 0.25
+    assert _box_limit(MPCConfig(), 10) == 0.0
+    for bad in (-0.1, float("nan")):
+        with pytest.raises(ValueError):
+            _box_limit(MPCConfig(max_weight=bad), 10)
+    for N, u in ((10, 0.1), (10, 0.05), (4, 0.25)):
+        with pytest.raises(ValueError):
+            _box_limit(MPCConfig(max_weight=u), N)
+    with pytest.raises(ValueError):
+        _box_limit(MPCConfig(max_weight=0.5, allow_short=True), 10)
+
+
+def test_dense_box_ipm_matches_the_project_oracle_when_the_bound_is_inactive():
+    """u = 1 never binds on the simplex: the helper reproduces the long-double oracle's objective."""
+    g = np.load(os.path.join(GOLD, "mpc_cfg1_N10_H5.npz"))
+    c, tau, short = g["config"]
+    assert not short
+    for b in range(4):
+        W, _, _ = box_ref.dense_box_ipm(g["w_prev"][b], g["yhat"][b], c, tau, 1.0)
+        f = box_ref.reference_objective(W, g["w_prev"][b], g["yhat"][b], c)
+        assert abs(f - g["obj"][b]) <= 1e-9 * (1 + abs(g["obj"][b])), (b, f, g["obj"][b])
+
+
+def test_every_issue_case_has_a_golden():
+    have = {os.path.basename(p) for p in BOX_FILES}
+    want = {f"box_N{N}_H{H}.npz" for N, H in ((3, 2), (10, 5), (13, 4), (16, 5), (30, 5), (65, 6), (100, 10), (129, 2),
+                                             (200, 10), (256, 5))}
+    assert have == want
+
+
+@pytest.mark.parametrize("path", BOX_FILES, ids=[os.path.basename(p) for p in BOX_FILES])
+def test_goldens_pinned(path):
+    g = np.load(path)
+    c, tau, u = (float(v) for v in g["config"])
+    B, H, N = g["yhat"].shape
+    assert g["yhat"].dtype == np.float32 and N * u > 1
+    active = False
+    for b in range(B):
+        wp = g["w_prev"][b]
+        assert bool(g["feasible"][b]) == box_ref.feasible(wp, H, N, tau, u)
+        if not g["feasible"][b]:
+            assert np.isnan(g["obj"][b]) and np.array_equal(g["W"][b], np.tile(wp, (H, 1)))
+            continue
+        W = g["W"][b]
+        assert np.abs(W.sum(1) - 1).max() <= 1e-12
+        assert W.min() >= -1e-12 and W.max() <= u + 1e-12
+        if tau > 0:
+            assert box_ref.turnover(W, wp).max() <= tau + 1e-12
+        assert g["obj"][b] == box_ref.reference_objective(W, wp, g["yhat"][b], c)
+        gp = box_ref.gap(W, wp, g["yhat"][b], c, tau, u)
+        print(f"{os.path.basename(path)} window {b}: gap {gp:.3e}")
+        assert gp <= 1e-8
+        active = active or W.max() > u - 1e-6
+        if N <= 30:
+            Wd, _, _ = box_ref.dense_box_ipm(wp, g["yhat"][b], c, tau, u)
+            f = box_ref.reference_objective(Wd, wp, g["yhat"][b], c)
+            assert abs(f - g["obj"][b]) <= 1e-9 * (1 + abs(g["obj"][b]))
+    assert active   # the limit binds somewhere in every file
