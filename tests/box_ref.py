@@ -12,6 +12,7 @@ The program (MPCConfig.max_weight = u, kmpc_solve_box), per window:
 * :func:`feasible` — LP feasibility of the lifted constraint set (scipy HiGHS dual simplex).
 * :func:`gap` — a linearisation certificate: an upper bound of ``p(W) - p*`` for ANY feasible W,
   whatever produced it, from one LP.
+* :func:`violated` — the feasibility bars (budget and turnover 1e-8, bounds 1e-9) in one place.
 """
 from __future__ import annotations
 
@@ -142,6 +143,28 @@ def feasible(w_prev, H, N, tau, u) -> bool:
 def turnover(W, w_prev):
     """||w_t - w_{t-1}||_1 per period, [H]."""
     return np.abs(np.diff(np.vstack([np.asarray(w_prev, np.float64), np.asarray(W, np.float64)]), axis=0)).sum(1)
+
+
+def violated(W, w_prev, tau, u) -> list:
+    """The project's feasibility bars on one window's W [H, N]: budget and turnover 1e-8, bounds
+    1e-9. Returns the bars W misses as text (empty: feasible), so ``assert not violated(...)``
+    names them."""
+    W = np.asarray(W, np.float64)
+    bad = []
+    if not np.isfinite(W).all():
+        return ["non-finite W"]
+    e = np.abs(W.sum(1) - 1).max()
+    if not e <= 1e-8:
+        bad.append(f"budget off by {e:.3e}")
+    if not W.min() >= -1e-9:
+        bad.append(f"min w {W.min():.3e}")
+    if not W.max() <= u + 1e-9:
+        bad.append(f"max w - u {W.max() - u:.3e}")
+    if tau > 0:
+        t = turnover(W, w_prev).max()
+        if not t <= tau + 1e-8:
+            bad.append(f"turnover - tau {t - tau:.3e}")
+    return bad
 
 
 def gap(W, w_prev, y, c, tau, u) -> float:

@@ -1,5 +1,6 @@
 """Goldens of the log-utility MPC solve with a per-asset position limit (kmpc_solve_box):
-``python tests/golden/make_box_golden.py`` writes tests/golden/box_N{N}_H{H}.npz. A one-off on the
+``python tests/golden/make_box_golden.py`` writes tests/golden/box_N{N}_H{H}.npz, every case or,
+with arguments ``N,H ...``, those files only (the others stay as committed). A one-off on the
 CPU (a few minutes: the dense interior point of tests/box_ref.py); nothing on the GPU side runs it.
 
 Per file: w_prev [B, N], yhat [B, H, N] float32, config = (c, tau, u), feasible [B] bool
@@ -30,6 +31,17 @@ CASES = [
     (129, 2, 1e-3, 0.3, 0.02, 2),    # HM = 2, 256 threads
     (200, 10, 1e-3, 0.2, 0.02, 1),   # HM = 10, 256 threads
     (256, 5, 1e-3, 0.3, 0.01, 1),    # HM = 5, 256 threads, N at its bound
+    # one or more per kernel and dispatch edge the ten above do not reach
+    (64, 10, 1e-3, 0.2, 0.05, 3),    # HM = 10, 64 threads, exact H, no inactive lane
+    (40, 8, 0.0, 0.3, 0.06, 3),      # HM = 10, 64 threads, ragged H, cap without cost
+    (120, 10, 1e-3, 0.15, 0.02, 2),  # HM = 10, 128 threads at the 128-lane stride (box arrays in registers);
+                                     # one infeasible window
+    (104, 7, 1e-3, 0.3, 0.03, 3),    # first N of the 128-lane stride, ragged H
+    (103, 10, 1e-3, 0.2, 0.03, 2),   # last N of the 104-lane stride
+    (96, 5, 1e-3, 0.2, 0.03, 3),     # HM = 5, 128 threads
+    (128, 3, 1e-3, 0.0, 0.02, 3),    # HM = 5, 128 threads, full block, ragged H, cost without cap
+    (70, 2, 1e-3, 0.3, 0.04, 3),     # HM = 2, 128 threads
+    (128, 1, 0.0, 0.0, 0.02, 3),     # HM = 2, 128 threads, H = 1, no turnover terms
 ]
 
 
@@ -40,8 +52,14 @@ def inputs(N, H, B):
     return w_prev, yhat
 
 
-def main():
+def main(argv):
+    only = {tuple(int(v) for v in a.split(",")) for a in argv}   # N,H ...: write these files only
+    unknown = only - {(N, H) for N, H, *_ in CASES}
+    if unknown:
+        raise SystemExit(f"no such case: {sorted(unknown)}")
     for N, H, c, tau, u, B in CASES:
+        if only and (N, H) not in only:
+            continue
         t0 = time.time()
         w_prev, yhat = inputs(N, H, B)
         feas = np.array([box_ref.feasible(w_prev[b], H, N, tau, u) for b in range(B)])
@@ -66,4 +84,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -120,7 +120,11 @@ def test_dense_box_ipm_matches_the_project_oracle_when_the_bound_is_inactive():
 def test_every_issue_case_has_a_golden():
     have = {os.path.basename(p) for p in BOX_FILES}
     want = {f"box_N{N}_H{H}.npz" for N, H in ((3, 2), (10, 5), (13, 4), (16, 5), (30, 5), (65, 6), (100, 10), (129, 2),
-                                             (200, 10), (256, 5))}
+                                             (200, 10), (256, 5),
+                                             # one or more per kernel and dispatch edge those do not reach
+                                             (64, 10), (40, 8), (120, 10), (104, 7), (103, 10), (96, 5), (128, 3),
+                                             (70, 2), (128, 1))}
+    assert len(want) == 19
     assert have == want
 
 
@@ -147,8 +151,83 @@ def test_goldens_pinned(path):
         print(f"{os.path.basename(path)} window {b}: gap {gp:.3e}")
         assert gp <= 1e-8
         active = active or W.max() > u - 1e-6
-        if N <= 30:
+        if N <= 128:
             Wd, _, _ = box_ref.dense_box_ipm(wp, g["yhat"][b], c, tau, u)
             f = box_ref.reference_objective(Wd, wp, g["yhat"][b], c)
             assert abs(f - g["obj"][b]) <= 1e-9 * (1 + abs(g["obj"][b]))
     assert active   # the limit binds somewhere in every file
+
+
+# ---- the checkers the device tests lean on (box_ref.gap, box_ref.violated) reject a wrong answer ----
+
+def _golden_window(name, b=0):
+    g = np.load(os.path.join(GOLD, name))
+    c, tau, u = (float(v) for v in g["config"])
+    assert g["feasible"][b]
+    return g["W"][b], g["w_prev"][b], g["yhat"][b], c, tau, u
+
+
+@pytest.mark.parametrize("name", ["box_N13_H4.npz", "box_N30_H5.npz", "box_N128_H3.npz"])
+def test_certificate_rejects_a_suboptimal_portfolio(name):
+    """1e-2 of weight moved in period 0 from a capped asset to the asset of lowest forecast: still
+    feasible (tau = 0 in these files, so only the bounds and the budget apply), about 1e-2 times
+    the spread of yhat (sd 0.015) worse, and the certificate must say so by ten times the objective
+    bar at the least. On the golden's own W the same certificate is below 1e-8."""
+    W, wp, y, c, tau, u = _golden_window(name)
+    assert tau == 0
+    hi = int(np.argmax(np.where(W[0] > u - 1e-6, y[0], -np.inf)))   # the capped asset of best forecast
+    lo = int(np.argmin(y[0]))
+    assert W[0, hi] > u - 1e-6 and W[0, lo] + 1e-2 <= u and hi != lo
+    V = W.copy()
+    V[0, hi] -= 1e-2
+    V[0, lo] += 1e-2
+    assert not box_ref.violated(V, wp, tau, u)
+    f = box_ref.reference_objective(V, wp, y, c)
+    bar = 1e-6 + 1e-5 * abs(f)
+    good, bad = box_ref.gap(W, wp, y, c, tau, u), box_ref.gap(V, wp, y, c, tau, u)
+    print(f"{name}: gap {good:.3e} at the golden, {bad:.3e} after the move, bar {bar:.3e}")
+    assert good <= 1e-8
+    assert bad > 10 * bar
+    # the certificate bounds the true loss from above
+    assert bad >= box_ref.reference_objective(W, wp, y, c) - f - 1e-12
+
+
+def test_feasibility_helper_holds_each_bar():
+    W, wp, y, c, tau, u = _golden_window("box_N10_H5.npz")
+    assert tau > 0
+    assert box_ref.violated(W, wp, tau, u) == []
+    i = int(np.argmax(W[0]))
+    j = int(np.argmin(W[0]))
+    assert W[0, i] > u - 1e-6 and i != j
+    # one entry at u + 1e-6 (the budget kept): the bounds bar, 1e-9, fails
+    V = W.copy()
+    V[0, j] -= u + 1e-6 - V[0, i]
+    V[0, i] = u + 1e-6
+    bad = box_ref.violated(V, wp, tau, u)
+    assert any(s.startswith("max w - u") for s in bad), bad
+    assert not any(s.startswith("budget") for s in bad), bad
+    # ... and 5e-10 past it passes
+    V = W.copy()
+    V[0, i] = u + 5e-10
+    assert not any(s.startswith("max w - u") for s in box_ref.violated(V, wp, tau, u))
+    # below zero
+    V = W.copy()
+    V[2, j] = -1e-8
+    assert any(s.startswith("min w") for s in box_ref.violated(V, wp, tau, u))
+    # the budget
+    V = W.copy()
+    V[1, j] += 1e-7
+    assert any(s.startswith("budget") for s in box_ref.violated(V, wp, tau, u))
+    # the turnover cap: a period that trades tau + 1e-6
+    V = np.tile(wp, (W.shape[0], 1))
+    assert box_ref.violated(V, wp, tau, 1.0) == []
+    k = int(np.argmax(wp))
+    V[0, k] -= (tau + 1e-6) / 2
+    V[0, j] += (tau + 1e-6) / 2
+    V[1:] = V[0]
+    assert wp[k] > (tau + 1e-6) / 2
+    bad = box_ref.violated(V, wp, tau, 1.0)
+    assert len(bad) == 1 and bad[0].startswith("turnover"), bad
+    assert box_ref.violated(V, wp, 0.0, 1.0) == []          # no cap, no turnover bar
+    V[0, 0] = np.nan
+    assert box_ref.violated(V, wp, tau, 1.0) == ["non-finite W"]

@@ -50,7 +50,7 @@ def _golden_run(path):
 
 
 def test_every_golden_is_here():
-    assert len(BOX_FILES) == 10
+    assert len(BOX_FILES) == 19
 
 
 @pytest.mark.parametrize("path", BOX_FILES, ids=IDS)
