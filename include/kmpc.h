@@ -370,6 +370,25 @@ int kmpc_solve_mv_ws(const kmpc_mv_desc* desc, const double* mu, const double* s
                      const double* w_prev, double* w_out, int* status, double* obj, int* iters,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- mean-variance MPC with a per-asset position limit (added within ABI 0.7.0, see the version
+ * note at the end): the program of kmpc_solve_mv_ws with one more constraint, w_t,i <= max_weight
+ * for every period and asset (0 <= w <= max_weight, no shorting). Arrays, statuses, the fallback
+ * and the workspace (kmpc_mv_workspace_bytes, unchanged) are those of kmpc_solve_mv_ws. The program
+ * has no turnover cap, so it is never infeasible: a w_prev above the limit trades down and pays the
+ * cost, and no new status appears. The limit is one more barrier inside the same interior point
+ * (slack max_weight - w from the iterate, its multiplier in a register), in both storage variants.
+ * Return codes, all decided before any launch (and before the B == 0 return), in this order:
+ *   - desc is checked as for kmpc_solve_mv_ws;
+ *   - max_weight NaN or <= 0: KMPC_ERR_INVALID;
+ *   - allow_short != 0: KMPC_ERR_UNSUPPORTED;
+ *   - max_weight >= 1 is an inactive bound: the call IS kmpc_solve_mv_ws with the same arguments,
+ *     bit-identical results;
+ *   - N * max_weight <= 1 (an empty feasible set, or the single point 1/N): KMPC_ERR_INVALID;
+ *   - then the workspace rule of kmpc_solve_mv_ws (KMPC_ERR_WORKSPACE past H*N = 128 without one). */
+int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double* mu, const double* sigma,
+                      size_t sigma_stride, const double* w_prev, double* w_out, int* status, double* obj,
+                      int* iters, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- Markowitz rolling moments: MarkowitzStrategy.rebalance (baselines.py:70-88) ------------ */
 /* For window b at test row t = ts[b]: returns r_s = z_s * std + mean (float32, as
  * destandardize_returns, data_finance.py:740-742) of the standardized rows z [T, ldz] (first N
@@ -397,7 +416,8 @@ const char* kmpc_strerror(int code);
    (kmpc_backtest_sweep), no layout change. kmpc_solve_box was added within 0.7.0: a new function
    only — no struct, enum or existing function changed, so every caller built against 0.7.0 keeps
    working unchanged and the version string did not move; a caller that needs the function checks
-   for the symbol (dlsym) rather than for a version. */
+   for the symbol (dlsym) rather than for a version. kmpc_solve_mv_box was added within 0.7.0 in the
+   same way: a new function only, kmpc_mv_desc and every existing function unchanged. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

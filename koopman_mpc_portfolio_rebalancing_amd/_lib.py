@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = ("kmpc_solve", "kmpc_rollout", "kmpc_window", "kmpc_workspace
                     "kmpc_backtest_step", "kmpc_backtest_metrics", "kmpc_standardize", "kmpc_strerror",
                     "kmpc_version", "kmpc_solve_mv", "kmpc_rolling_moments", "kmpc_solve_mv_ws",
                     "kmpc_mv_workspace_bytes", "kmpc_gross_returns", "kmpc_backtest_run",
-                    "kmpc_backtest_sweep", "kmpc_solve_box")
+                    "kmpc_backtest_sweep", "kmpc_solve_box", "kmpc_solve_mv_box")
 
 PATH_AUTO, PATH_REGISTER, PATH_LARGE, PATH_REGISTER_UNPACKED = 0, 1, 2, 3   # kmpc_solve_desc.path
 PRECISION_AUTO, PRECISION_F64, PRECISION_MIXED = 0, 1, 2   # kmpc_solve_desc.precision
@@ -48,8 +48,8 @@ PACK_MIN_B = 512     # KMPC_PACK_MIN_B: AUTO packs N <= 32 windows 2-4 per wave 
 # library would read them past its structs' end; 0.4.0 added enum values only (KMPC_PRECISION_MIXED,
 # KMPC_DTYPE_F32_F32MFMA), no layout change; 0.5.0 added kmpc_backtest_run;
 # 0.6.0 enum values only (KMPC_LATENT_SEQUENTIAL); 0.7.0 added kmpc_backtest_sweep; kmpc_solve_box
-# was added within 0.7.0 (a new function only: nothing a 0.7.0 caller uses changed); a 0.7.0 library
-# built before it lacks the symbol, which load() reports
+# and kmpc_solve_mv_box were added within 0.7.0 (new functions only: nothing a 0.7.0 caller uses
+# changed); a 0.7.0 library built before them lacks the symbols, which load() reports
 ABI_VERSION = "0.7.0"
 
 
@@ -150,6 +150,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
         raise KmpcError(f"{p} has no kmpc_solve_box (added within ABI {ABI_VERSION}): rebuild the library")
     L.kmpc_solve_box.argtypes = [ctypes.POINTER(SolveDesc), ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_solve_box.restype = ctypes.c_int
+    if not hasattr(L, "kmpc_solve_mv_box"):
+        raise KmpcError(f"{p} has no kmpc_solve_mv_box (added within ABI {ABI_VERSION}): rebuild the library")
+    L.kmpc_solve_mv_box.argtypes = [ctypes.POINTER(MvDesc), ctypes.c_double, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
+                                    vp]
+    L.kmpc_solve_mv_box.restype = ctypes.c_int
     if path is None:
         _lib = L
     return L

@@ -10,8 +10,8 @@ encoder / decoder and the latent operator A^T (row-vector convention, z <- z @ A
 
 Mirrors ``MarkowitzStrategy`` (baselines.py:24-106): the rolling 60-row mean / covariance of the
 de-standardized current returns (kmpc_rolling_moments) and the H = 1 mean-variance solve
-(kmpc_solve_mv, mpc.py:119-184) run on the device, for one window (``rebalance``) or many
-(``rebalance_batch``).
+(kmpc_solve_mv, mpc.py:119-184; kmpc_solve_mv_box under a per-asset position limit) run on the
+device, for one window (``rebalance``) or many (``rebalance_batch``).
 """
 from __future__ import annotations
 
@@ -97,22 +97,42 @@ def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None
     return mu, sigma, valid
 
 
-class MarkowitzStrategy(Strategy):
+class _LimitKeyword(type(Strategy)):
+    """``MarkowitzStrategy(..., max_weight=u)``: the keyword is taken by the class call and applied
+    with ``set_max_weight`` — ``__init__`` keeps the reference's three arguments exactly
+    (baselines.py:33-37), as the drop-in surface promises."""
+
+    def __call__(cls, *args, max_weight: float = 0.0, **kwargs):
+        obj = super().__call__(*args, **kwargs)
+        obj.set_max_weight(max_weight)
+        return obj
+
+
+class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
     """Classic mean-variance strategy (baselines.py:24-106) on the device.
 
     Same constructor and ``mpc_config`` (H = 1, gamma = risk_aversion, baselines.py:39-45);
     ``rebalance`` follows baselines.py:48-106 (hold when fewer than 5 past rows, rolling moments
-    of the last ``lookback_window`` rows, W[0] of the mean-variance solve).
+    of the last ``lookback_window`` rows, W[0] of the mean-variance solve). ``max_weight`` (keyword,
+    not in the reference) is the per-asset position limit of ``MPCConfig.max_weight``: every target
+    keeps w <= max_weight (long-only, N * max_weight > 1; 0: none), so the baseline runs under the
+    same limit as the MPC strategies.
     """
 
     def __init__(self, risk_aversion: float = 1.0, cost_coeff: float = 0.001, allow_short: bool = False):
         self.risk_aversion = risk_aversion
         self.cost_coeff = cost_coeff
         self.allow_short = allow_short
+        self.max_weight = 0.0
         self.mpc_config = MPCConfig(horizon=1, gamma=risk_aversion, cost_coeff=cost_coeff,
                                     allow_short=allow_short, solver="ECOS")
         self._dev = None
         self._cache = (None, None)
+
+    def set_max_weight(self, max_weight: float) -> None:
+        """Set the per-asset position limit on the strategy and in its ``mpc_config``."""
+        self.max_weight = max_weight
+        self.mpc_config.max_weight = max_weight
 
     def _device(self) -> torch.device:
         if self._dev is None:

@@ -216,6 +216,24 @@ int kmpc_solve_mv_ws(const kmpc_mv_desc* desc, const double* mu, const double* s
                                  ws_bytes, (hipStream_t)stream);
 }
 
+int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double* mu, const double* sigma,
+                      size_t sigma_stride, const double* w_prev, double* w_out, int* status, double* obj,
+                      int* iters, void* workspace, size_t ws_bytes, void* stream) {
+    // every rule is decided before any launch (and before the B == 0 return), in kmpc_solve_box's order
+    if (!desc || desc->B < 0 || desc->N < 1 || desc->H < 1) return KMPC_ERR_INVALID;
+    if (desc->H > KMPC_MV_MAX_H || desc->N * desc->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    if (desc->allow_short) return KMPC_ERR_UNSUPPORTED;
+    if (max_weight >= 1.0)   // an inactive bound: the plain solve
+        return kmpc_solve_mv_ws(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
+                                ws_bytes, stream);
+    if (!((double)desc->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
+    if (desc->B == 0) return KMPC_OK;
+    if (!mu || !sigma || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
+    return kmpc::mv_solve_launch(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
+                                 ws_bytes, (hipStream_t)stream, max_weight);
+}
+
 int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int ldz,
                          const float* mean, const float* std, const int* ts,
                          double* mu, double* sigma, int* valid, void* stream) {

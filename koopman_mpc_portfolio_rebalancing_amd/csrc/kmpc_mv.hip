@@ -3,7 +3,8 @@
 //
 // Program per window (mpc.py:128, 145-172):
 //   maximize  sum_t [ w_t . mu_t - gamma w_t' Sigma w_t ] - c sum_t ||w_t - w_{t-1}||_1
-//   s.t.      1'w_t = 1, w_t >= 0 unless allow_short          (no turnover cap), w_{-1} = w_prev.
+//   s.t.      1'w_t = 1, w_t >= 0 unless allow_short          (no turnover cap), w_{-1} = w_prev;
+//             with a position limit (kmpc_solve_mv_box, the BOX kernels) also w_t <= u, long-only.
 // One workgroup per window, one element (t, i) of W per thread (n = H N <= 1024). Algorithm:
 // Mehrotra predictor-corrector primal-dual interior point on the epigraph form (s_ti >= |d_ti|,
 // d = w_t - w_{t-1}), float64, objective scaled by max(|mu|, 2 gamma |Sigma|, c). The s rows and
@@ -41,6 +42,7 @@ struct MvArgs {
     int* iters;
     double* ws;             // workspace slabs (global-M variant)
     size_t slab;            // doubles per slab
+    double max_weight;      // BOX kernels: the per-asset position limit u (w <= u), N u > 1
 };
 
 constexpr int MV_SLOTS = 512;   // windows in flight of the global-M variant
@@ -143,7 +145,9 @@ __device__ double chol_solve(const double* M, int n, double b, double* vec) {
 
 
 // One window. GM: M and Y in the block's workspace slab (else in LDS after the small arrays).
-template <bool GM>
+// BOX: the position limit w <= u (long-only callers), one more barrier on w treated as w >= 0 is:
+// slack x5 = u - w taken from the iterate (no slack variable), multiplier l5 in a register.
+template <bool GM, bool BOX>
 __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     const int N = a.N, H = a.H, n = N * H;
     double* vec = lds;                      // [n] broadcast vector
@@ -204,13 +208,16 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
         }
     } else if (nonfinite == 0.0 && isfinite(a.gamma) && isfinite(a.c)) {
         double w = act ? 0.5 * (hw ? fmax(wpi, 0.0) : wpi) + 0.5 / N : 0.0;
+        if constexpr (BOX) w = fmin(w, 0.5 * (a.max_weight + 1.0 / N));   // strictly inside: 1 / N < u
         double wm = prev_period(w, vec, k, n, N, wpi);
         double s = (act && hs) ? fabs(w - wm) + 1.0 / N : 0.0;
         // slacks of the two |d| rows kept as variables (no cancellation in s -+ d near the optimum)
         double z2 = (act && hs) ? fmax(s - (w - wm), 1e-2) : 1.0, z3 = (act && hs) ? fmax(s + (w - wm), 1e-2) : 1.0;
         double l1 = (act && hw) ? 1.0 : 0.0, l2 = (act && hs) ? 1.0 : 0.0, l3 = l2;
+        double l5 = 0.0, x5 = 1.0;   // BOX only (l5 stays 0 on the inactive lanes)
+        if constexpr (BOX) l5 = act ? 1.0 : 0.0;
         if (k < H) nu[k] = 0.0;
-        const int mcon = (hw ? n : 0) + (hs ? 2 * n : 0);
+        const int mcon = (hw ? n : 0) + (hs ? 2 * n : 0) + (BOX ? n : 0);
         const double inv_m = 1.0 / (mcon > 0 ? mcon : 1);
 
         for (it = 0; it < a.max_iter; ++it) {
@@ -237,9 +244,15 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             if (k < H) rpv[k] = pv[k] - 1.0;
             double prmax = 0.0;
             for (int q = 0; q < H; ++q) prmax = fmax(prmax, fabs(pv[q] - 1.0));
-            const double rw = act ? -mus + g2 * Sw - l1 + eta - etan + nu[t] : 0.0;
+            double rw = act ? -mus + g2 * Sw - l1 + eta - etan + nu[t] : 0.0;
             const double rs = (act && hs) ? cs - l2 - l3 : 0.0;
-            const double mu_c = block_sum(act ? w * l1 + z2 * l2 + z3 * l3 : 0.0, red) * inv_m;
+            double comp = act ? w * l1 + z2 * l2 + z3 * l3 : 0.0;
+            if constexpr (BOX) {
+                x5 = a.max_weight - w;
+                rw += l5;
+                comp += x5 * l5;
+            }
+            const double mu_c = block_sum(comp, red) * inv_m;
             const double rd = block_max(fmax(fmax(fabs(rw), fabs(rs)), fmax(fabs(rg2), fabs(rg3))), red);
             const double wabs = block_max(act ? fabs(w) : 0.0, red);
             const double merit = fmax(mu_c, fmax(rd, prmax));
@@ -255,7 +268,8 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             if (mu_c < a.tol && rd < 10.0 * a.tol && prmax < 10.0 * a.tol) break;
 
             // ---- factor: M = 2 gamma (I (x) Sigma) + diag(W1) + D' diag(E) D ----
-            const double W1 = (act && hw) ? l1 / w : 0.0;
+            double W1 = (act && hw) ? l1 / w : 0.0;
+            if constexpr (BOX) W1 += l5 / x5;
             const double al = (act && hs) ? l2 / z2 : 0.0, be = (act && hs) ? l3 / z3 : 0.0;
             const double P = (act && hs) ? 1.0 / (al + be) : 0.0;
             const double E = 4.0 * al * be * P;
@@ -347,12 +361,15 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             double rc1 = (act && hw) ? w * l1 : 0.0, rc2 = (act && hs) ? z2 * l2 : 0.0;
             double rc3 = (act && hs) ? z3 * l3 : 0.0;
             double dw = 0.0, ds = 0.0, dl1 = 0.0, dl2 = 0.0, dl3 = 0.0, step = 0.0, prev_dw = 0.0;
+            double rc5 = 0.0, dl5 = 0.0;
+            if constexpr (BOX) rc5 = x5 * l5;
             for (int pass = 0; pass < 2; ++pass) {
                 const double p2 = rc2 / z2 + al * rg2, p3 = rc3 / z3 + be * rg3;
                 const double qs = (act && hs) ? -rs - p2 - p3 : 0.0;
                 const double v = (act && hs) ? (be - al) * P * qs + p3 - p2 : 0.0;
                 const double vn = next_period(v, vec, k, n, N);
-                const double rhs = act ? -rw - (hw ? rc1 / w : 0.0) - (v - vn) : 0.0;
+                double rhs = act ? -rw - (hw ? rc1 / w : 0.0) - (v - vn) : 0.0;
+                if constexpr (BOX) rhs += rc5 / x5;
                 const double x = chol_solve(M, n, rhs, vec);
                 period_sums(x, vec, pv, k, n, N, H);
                 if (k == 0) {   // dnu = S^{-1} (A x + r_p)
@@ -379,22 +396,31 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                 dl1 = (act && hw) ? -(l1 * dw + rc1) / w : 0.0;
                 dl2 = (act && hs) ? -(l2 * dz2 + rc2) / z2 : 0.0;
                 dl3 = (act && hs) ? -(l3 * dz3 + rc3) / z3 : 0.0;
+                if constexpr (BOX) dl5 = (-rc5 + l5 * dw) / x5;
                 double am = 1e300;
                 if (act && hw) { am = to_bound(w, dw, am); am = to_bound(l1, dl1, am); }
                 if (act && hs) {
                     am = to_bound(z2, dz2, am); am = to_bound(z3, dz3, am);
                     am = to_bound(l2, dl2, am); am = to_bound(l3, dl3, am);
                 }
+                if constexpr (BOX) {
+                    if (act) { am = to_bound(x5, -dw, am); am = to_bound(l5, dl5, am); }
+                }
                 am = block_min(am, red);
                 if (pass == 1) { step = fmin(1.0, 0.99 * am); break; }
                 const double ap = fmin(1.0, am);
-                const double mua = block_sum(act ? (w + ap * dw) * (l1 + ap * dl1) + (z2 + ap * dz2) * (l2 + ap * dl2) +
-                                                       (z3 + ap * dz3) * (l3 + ap * dl3) : 0.0, red) * inv_m;
+                double compa = act ? (w + ap * dw) * (l1 + ap * dl1) + (z2 + ap * dz2) * (l2 + ap * dl2) +
+                                         (z3 + ap * dz3) * (l3 + ap * dl3) : 0.0;
+                if constexpr (BOX) compa += (x5 - ap * dw) * (l5 + ap * dl5);
+                const double mua = block_sum(compa, red) * inv_m;
                 double sg = mua / mu_c;
                 sg = sg * sg * sg;
                 const double smu = sg * mu_c;
                 if (act && hw) rc1 = w * l1 + dw * dl1 - smu;
                 if (act && hs) { rc2 = z2 * l2 + dz2 * dl2 - smu; rc3 = z3 * l3 + dz3 * dl3 - smu; }
+                if constexpr (BOX) {
+                    if (act) rc5 = x5 * l5 - dw * dl5 - smu;
+                }
             }
             w += step * dw;
             s += step * ds;
@@ -405,6 +431,7 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             l1 += step * dl1;
             l2 += step * dl2;
             l3 += step * dl3;
+            if constexpr (BOX) l5 += step * dl5;
             __syncthreads();
             if (k < H) nu[k] += step * dnu[k];
             __syncthreads();
@@ -424,16 +451,16 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     }
 }
 
-template <int MAXT, bool GM>
+template <int MAXT, bool GM, bool BOX>
 __global__ void __launch_bounds__(MAXT) mv_ipm_kernel(MvArgs a) {
     extern __shared__ double lds[];
     if (GM) {
         for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-            mv_window<true>(a, b, lds);
+            mv_window<true, BOX>(a, b, lds);
             __syncthreads();
         }
     } else {
-        mv_window<false>(a, blockIdx.x, lds);
+        mv_window<false, BOX>(a, blockIdx.x, lds);
     }
 }
 
@@ -496,7 +523,7 @@ size_t mv_workspace_bytes(const kmpc_mv_desc* d) {
 
 int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma, size_t sigma_stride,
                     const double* w_prev, double* w_out, int* status, double* obj, int* iters,
-                    void* ws, size_t ws_bytes, hipStream_t stream) {
+                    void* ws, size_t ws_bytes, hipStream_t stream, double max_weight) {
     MvArgs a;
     a.B = d->B; a.N = d->N; a.H = d->H;
     a.gamma = d->gamma; a.c = d->cost_coeff;
@@ -507,15 +534,23 @@ int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma
     a.mu = mu; a.sigma = sigma; a.sigma_stride = sigma_stride; a.wp = w_prev;
     a.wout = w_out; a.status = status; a.obj = obj; a.iters = iters;
     a.ws = (double*)ws; a.slab = mv_slab(d->N, d->H);
+    a.max_weight = max_weight;
+    const bool box = max_weight > 0.0;   // kmpc_solve_mv_box (long-only, N u > 1, u < 1); else the plain kernels
     const int n = d->N * d->H;
     const int nt = 64 * ((n + 63) / 64);
     if (mv_in_lds(d->N, d->H)) {
-        hipLaunchKernelGGL((mv_ipm_kernel<128, false>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
+        if (box)
+            hipLaunchKernelGGL((mv_ipm_kernel<128, false, true>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
+        else
+            hipLaunchKernelGGL((mv_ipm_kernel<128, false, false>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
     } else {
         if (n > 1024 || mv_small_bytes(d->N, d->H) > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
         if (!ws || ws_bytes < mv_workspace_bytes(d)) return KMPC_ERR_WORKSPACE;
         const int grid = d->B < MV_SLOTS ? d->B : MV_SLOTS;
-        hipLaunchKernelGGL((mv_ipm_kernel<1024, true>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
+        if (box)
+            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, true>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
+        else
+            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, false>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
     }
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }

@@ -37,14 +37,14 @@ class MPCConfig:
     solver_path: int = 0  # kmpc_solve_desc.path: 0 by shape, 1 register IPM (no presolve), 2 large-window IPM, 3 register IPM without lane-group packing
     precision: str = "auto"  # kmpc_solve_desc.precision: "mixed" (float32 warm-start phase + float64 finish where available), "f64", or "auto" (mixed from 2,048 windows per call, else f64)
     mu_handoff: float = 0.0  # float32 -> float64 handoff at mu <= mu_handoff (0 -> kernel default 3e-5)
-    max_weight: float = 0.0  # per-asset position limit w <= max_weight of the log-utility solve (kmpc_solve_box); 0 or >= 1: none
+    max_weight: float = 0.0  # per-asset position limit w <= max_weight of the log-utility (kmpc_solve_box) and the mean-variance (kmpc_solve_mv_box) solves; 0 or >= 1: none
 
 
 def _box_limit(config: MPCConfig, N: int) -> float:
     """The active per-asset position limit of `config` for N assets, or 0.0 when it has none
     (max_weight 0, or >= 1: the simplex already bounds every weight by 1). kmpc_solve_desc cannot
     carry the limit, so every caller that turns an MPCConfig into a solve goes through here and
-    then through kmpc_solve_box. Raises ValueError where no program exists: a negative or NaN
+    then through kmpc_solve_box (kmpc_mv_desc cannot either: kmpc_solve_mv_box). Raises ValueError where no program exists: a negative or NaN
     limit, N * max_weight <= 1 (empty set, or the single point 1/N), or together with allow_short."""
     u = float(getattr(config, "max_weight", 0.0))
     if u != u or u < 0.0:
@@ -206,15 +206,17 @@ def solve_mpc_mean_variance_batched(
     return_full: bool = False,
     with_iters: bool = False,
 ):
-    """Batched mean-variance solve on the device (kmpc_solve_mv).
+    """Batched mean-variance solve on the device (kmpc_solve_mv_ws; kmpc_solve_mv_box with a
+    position limit).
 
     Args:
         current_weights: [B, N] device tensor (float64; other dtypes are converted).
         mu: [B, H, N] expected returns (the reference passes predicted log-returns / the rolling
             mean as mu, mpc.py:150-155); computed in float64.
         cov_matrix: [B, N, N] per-window covariance, or one shared [N, N] (mpc.py:123).
-        config: MPCConfig (gamma, cost_coeff, allow_short; max_turnover is not part of this
-            program in the reference either).
+        config: MPCConfig (gamma, cost_coeff, allow_short, and max_weight: the per-asset position
+            limit w <= max_weight, long-only, N * max_weight > 1 — ValueError otherwise; 0 or >= 1:
+            none; max_turnover is not part of this program in the reference either).
         return_full: return W [B, H, N] instead of W[:, 0].
 
     Returns:
@@ -255,12 +257,18 @@ def solve_mpc_mean_variance_batched(
     d.tol = float(getattr(config, "mv_tol", 1e-10))
     d.return_full_W = int(bool(return_full))
     L = _lib.load()
+    u = _box_limit(config, N)
     with torch.cuda.device(dev):
         nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(d)))
         ws = _workspace(dev, nws) if nws else None
-        rc = L.kmpc_solve_mv_ws(ctypes.byref(d), mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
-                                W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                                ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
+        if u:   # the position limit: the BOX form of the same kernels, same workspace
+            rc = L.kmpc_solve_mv_box(ctypes.byref(d), u, mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
+                                     W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                                     ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
+        else:
+            rc = L.kmpc_solve_mv_ws(ctypes.byref(d), mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
+                                    W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                                    ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
     _lib.check(rc)
     if with_iters:
         return W, status, value, iters
