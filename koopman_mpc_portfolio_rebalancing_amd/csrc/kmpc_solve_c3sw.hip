@@ -4,6 +4,9 @@
 #ifndef KMPC_SCHUR_BCAST_F64   // as kmpc_solve_c3.hip
 #define KMPC_SCHUR_BCAST_F64 1
 #endif
+#ifndef KMPC_FD_WAIT_ONCE_F64   // the column update's wait states at every chunk, as before: the once-per-step
+#define KMPC_FD_WAIT_ONCE_F64 0   // form moved the sibling backtest kernel's allocation and ran behind
+#endif
 #include "kmpc_solve_kernel.h"
 #include "kmpc_bt_sweep.h"
 

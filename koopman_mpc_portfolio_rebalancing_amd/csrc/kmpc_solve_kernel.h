@@ -430,47 +430,68 @@ __device__ __forceinline__ float row_bcast(float v, int j) {
 // in every lane's own 16-lane row: the row_newbcast folded into the FMA's first operand
 // (v_fmac_f32_dpp / v_fmac_f64_dpp, one instruction per element). The compiler does not fold the
 // DPP move itself (gfx9 selects the three-address v_fma, which has no DPP form), so the
-// instructions are written out, in chunks of 8, 4, 2, 1 elements. Each chunk opens with the two
-// wait states a DPP read needs after a VALU write of its source (the hazard the compiler covers
-// for its own DPP moves, not inside asm), so no chunk depends on what was scheduled before it.
+// instructions are written out, in chunks of 8, 4, 2, 1 elements. A step's first chunk (LEAD)
+// opens with the two wait states a DPP read needs after a VALU write of its source (the hazard the
+// compiler covers for its own DPP moves, not inside asm), so it does not depend on what was
+// scheduled before it. The step's later chunks read the same ca, cb through DPP and nothing else:
+// the first chunk, which needs both, stands between their last write and any later chunk, and
+// whatever else is scheduled there only adds distance, so they open with no wait (56 of the 85
+// s_nop of a KM = 30 factorisation, all on wave 0's serial chain).
 #define KMPC_FD(op, i) "\n\t" op " %[g" #i "], %[c" #i "], %[nl] row_newbcast:%[r" #i "] row_mask:0xf bank_mask:0xf"
 #define KMPC_FD_OUT(i) [g##i] "+v"(g[K0 + i])
 #define KMPC_FD_IN(i) [c##i] "v"(K0 + i < 16 ? ca : cb), [r##i] "n"((K0 + i) & 15)
-#define KMPC_FD_CHUNKS(op)                                                                                          \
+#define KMPC_FD_CHUNKS(w, op)                                                                                        \
     if constexpr (CNT == 8)                                                                                         \
-        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3) KMPC_FD(op, 4)                    \
+        asm(w KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3) KMPC_FD(op, 4)                            \
             KMPC_FD(op, 5) KMPC_FD(op, 6) KMPC_FD(op, 7)                                                            \
             : KMPC_FD_OUT(0), KMPC_FD_OUT(1), KMPC_FD_OUT(2), KMPC_FD_OUT(3), KMPC_FD_OUT(4),                       \
               KMPC_FD_OUT(5), KMPC_FD_OUT(6), KMPC_FD_OUT(7)                                                        \
             : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1), KMPC_FD_IN(2), KMPC_FD_IN(3), KMPC_FD_IN(4),              \
               KMPC_FD_IN(5), KMPC_FD_IN(6), KMPC_FD_IN(7));                                                         \
     else if constexpr (CNT == 4)                                                                                    \
-        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3)                                   \
+        asm(w KMPC_FD(op, 0) KMPC_FD(op, 1) KMPC_FD(op, 2) KMPC_FD(op, 3)                                           \
             : KMPC_FD_OUT(0), KMPC_FD_OUT(1), KMPC_FD_OUT(2), KMPC_FD_OUT(3)                                        \
             : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1), KMPC_FD_IN(2), KMPC_FD_IN(3));                            \
     else if constexpr (CNT == 2)                                                                                    \
-        asm("s_nop 1" KMPC_FD(op, 0) KMPC_FD(op, 1)                                                                 \
+        asm(w KMPC_FD(op, 0) KMPC_FD(op, 1)                                                                         \
             : KMPC_FD_OUT(0), KMPC_FD_OUT(1) : [nl] "v"(nl), KMPC_FD_IN(0), KMPC_FD_IN(1));                         \
     else                                                                                                            \
-        asm("s_nop 1" KMPC_FD(op, 0) : KMPC_FD_OUT(0) : [nl] "v"(nl), KMPC_FD_IN(0))
-template <int CNT, int K0, int KM>
+        asm(w KMPC_FD(op, 0) : KMPC_FD_OUT(0) : [nl] "v"(nl), KMPC_FD_IN(0))
+template <int CNT, int K0, bool LEAD, int KM>
 __device__ __forceinline__ void fmac_dpp_chunk(float (&g)[KM], float ca, float cb, float nl) {
-    KMPC_FD_CHUNKS("v_fmac_f32_dpp");
+    if constexpr (LEAD) { KMPC_FD_CHUNKS("s_nop 1", "v_fmac_f32_dpp"); }
+    else { KMPC_FD_CHUNKS("", "v_fmac_f32_dpp"); }
 }
-template <int CNT, int K0, int KM>
+template <int CNT, int K0, bool LEAD, int KM>
 __device__ __forceinline__ void fmac_dpp_chunk(double (&g)[KM], double ca, double cb, double nl) {
-    KMPC_FD_CHUNKS("v_fmac_f64_dpp");
+    if constexpr (LEAD) { KMPC_FD_CHUNKS("s_nop 1", "v_fmac_f64_dpp"); }
+    else { KMPC_FD_CHUNKS("", "v_fmac_f64_dpp"); }
 }
 #undef KMPC_FD_CHUNKS
 #undef KMPC_FD_IN
 #undef KMPC_FD_OUT
 #undef KMPC_FD
-template <int K0, int KM, class T>
+// ONCE: the wait states once per step (above), per precision (0: every chunk and every step
+// opens with them, the earlier form). One setting per translation unit: in the C3 unit the float64
+// form is ahead in the fused mixed kernel and behind in the float64-only and path-persistent
+// backtest kernels, whose register allocation it moves.
+#ifndef KMPC_FD_WAIT_ONCE_F32
+#define KMPC_FD_WAIT_ONCE_F32 1
+#endif
+#ifndef KMPC_FD_WAIT_ONCE_F64
+#define KMPC_FD_WAIT_ONCE_F64 1
+#endif
+template <class T>
+constexpr bool fd_wait_once() { return sizeof(T) == 4 ? KMPC_FD_WAIT_ONCE_F32 != 0 : KMPC_FD_WAIT_ONCE_F64 != 0; }
+template <int K0, bool ONCE, bool LEAD = true, int KM, class T>
 __device__ __forceinline__ void fmac_dpp_from(T (&g)[KM], T ca, T cb, T nl) {
     constexpr int n = KM - K0, CNT = n >= 8 ? 8 : (n >= 4 ? 4 : (n >= 2 ? 2 : 1));
     if constexpr (n > 0) {
-        fmac_dpp_chunk<CNT, K0>(g, ca, cb, nl);
-        fmac_dpp_from<K0 + CNT>(g, ca, cb, nl);
+        fmac_dpp_chunk<CNT, K0, LEAD>(g, ca, cb, nl);
+        // (no instruction: the later chunks take ca, cb from here, and this reads what the first
+        // chunk wrote, so the scheduler cannot move one of them ahead of the first chunk)
+        if constexpr (ONCE && LEAD && n > CNT) asm("" : "+v"(ca), "+v"(cb) : "v"(g[K0]));
+        fmac_dpp_from<K0 + CNT, ONCE, !ONCE>(g, ca, cb, nl);
     }
 }
 template <int GL, class T>
@@ -551,6 +572,107 @@ __device__ __forceinline__ void rs_level(T (&v)[M], int& n, int& slot) {
     }
 }
 
+// The float32 reduce-scatter of whole-wave windows with its exchanges written out (per unit, as
+// KMPC_SCHUR_BCAST_*; on in kmpc_solve_c3.hip). The same pairs and the same sums as
+// rs_level, so the totals are bit-identical (an upper lane adds partner + own instead of own +
+// partner). What changes is the instruction stream of a lone wave:
+//  - the 32- and 16-lane levels issue their permlane swaps back to back, up to sixteen pairs per
+//    statement: the two wait states a swap needs after a VALU write of its operands are paid once
+//    per statement instead of once per swap (the compiler places copy, s_nop, swap, add pair by
+//    pair);
+//  - the row_mirror / row_half_mirror levels exchange and add in one v_add_f32_dpp per half (the
+//    bank masks of the moves they replace) instead of two bank-masked moves and an add.
+// Every statement opens with the wait states its lane reads need (as fmac_dpp_chunk), so no
+// hazard depends on what was scheduled before it.
+#ifndef KMPC_RS_ASM_F32
+#define KMPC_RS_ASM_F32 0
+#endif
+#define KMPC_RS_SW(op, i) "\n\t" op " %[a" #i "], %[b" #i "]"
+#define KMPC_RS_SW_IO(i) [a##i] "+v"(v[J0 + i]), [b##i] "+v"(v[J0 + H + i])
+#define KMPC_RS_SWAPS(op)                                                                                           \
+    if constexpr (CNT == 16)                                                                                        \
+        asm("s_nop 1" KMPC_RS_SW(op, 0) KMPC_RS_SW(op, 1) KMPC_RS_SW(op, 2) KMPC_RS_SW(op, 3) KMPC_RS_SW(op, 4)     \
+            KMPC_RS_SW(op, 5) KMPC_RS_SW(op, 6) KMPC_RS_SW(op, 7) KMPC_RS_SW(op, 8) KMPC_RS_SW(op, 9)               \
+            KMPC_RS_SW(op, 10) KMPC_RS_SW(op, 11) KMPC_RS_SW(op, 12) KMPC_RS_SW(op, 13) KMPC_RS_SW(op, 14)          \
+            KMPC_RS_SW(op, 15)                                                                                      \
+            : KMPC_RS_SW_IO(0), KMPC_RS_SW_IO(1), KMPC_RS_SW_IO(2), KMPC_RS_SW_IO(3), KMPC_RS_SW_IO(4),             \
+              KMPC_RS_SW_IO(5), KMPC_RS_SW_IO(6), KMPC_RS_SW_IO(7), KMPC_RS_SW_IO(8), KMPC_RS_SW_IO(9),             \
+              KMPC_RS_SW_IO(10), KMPC_RS_SW_IO(11), KMPC_RS_SW_IO(12), KMPC_RS_SW_IO(13), KMPC_RS_SW_IO(14),        \
+              KMPC_RS_SW_IO(15));                                                                                   \
+    else if constexpr (CNT == 8)                                                                                     \
+        asm("s_nop 1" KMPC_RS_SW(op, 0) KMPC_RS_SW(op, 1) KMPC_RS_SW(op, 2) KMPC_RS_SW(op, 3) KMPC_RS_SW(op, 4)     \
+            KMPC_RS_SW(op, 5) KMPC_RS_SW(op, 6) KMPC_RS_SW(op, 7)                                                   \
+            : KMPC_RS_SW_IO(0), KMPC_RS_SW_IO(1), KMPC_RS_SW_IO(2), KMPC_RS_SW_IO(3), KMPC_RS_SW_IO(4),             \
+              KMPC_RS_SW_IO(5), KMPC_RS_SW_IO(6), KMPC_RS_SW_IO(7));                                                \
+    else if constexpr (CNT == 4)                                                                                    \
+        asm("s_nop 1" KMPC_RS_SW(op, 0) KMPC_RS_SW(op, 1) KMPC_RS_SW(op, 2) KMPC_RS_SW(op, 3)                       \
+            : KMPC_RS_SW_IO(0), KMPC_RS_SW_IO(1), KMPC_RS_SW_IO(2), KMPC_RS_SW_IO(3));                              \
+    else if constexpr (CNT == 2)                                                                                    \
+        asm("s_nop 1" KMPC_RS_SW(op, 0) KMPC_RS_SW(op, 1) : KMPC_RS_SW_IO(0), KMPC_RS_SW_IO(1));                    \
+    else                                                                                                            \
+        asm("s_nop 1" KMPC_RS_SW(op, 0) : KMPC_RS_SW_IO(0))
+// pairs (v[j], v[j + H]), J0 <= j < H, swapped in place over the wave's halves (D = 32) / rows (16)
+template <int D, int J0, int H, int M>
+__device__ __forceinline__ void rs_swap_from(float (&v)[M]) {
+    constexpr int n = H - J0, CNT = n >= 16 ? 16 : (n >= 8 ? 8 : (n >= 4 ? 4 : (n >= 2 ? 2 : 1)));
+    if constexpr (n > 0) {
+        if constexpr (D == 32) { KMPC_RS_SWAPS("v_permlane32_swap_b32"); }
+        else { KMPC_RS_SWAPS("v_permlane16_swap_b32"); }
+        rs_swap_from<D, J0 + CNT, H>(v);
+    }
+}
+#undef KMPC_RS_SWAPS
+#undef KMPC_RS_SW_IO
+#undef KMPC_RS_SW
+// v[j] = own v[j] + the partner's (lower banks) / own v[j + H] + the partner's (upper banks)
+#define KMPC_RS_AD(c, lm, um, i)                                                                                    \
+    "\n\tv_add_f32_dpp %[a" #i "], %[a" #i "], %[a" #i "] " c " row_mask:0xf bank_mask:" lm                          \
+    "\n\tv_add_f32_dpp %[a" #i "], %[b" #i "], %[b" #i "] " c " row_mask:0xf bank_mask:" um
+#define KMPC_RS_AD_OUT(i) [a##i] "+v"(v[J0 + i])
+#define KMPC_RS_AD_IN(i) [b##i] "v"(v[J0 + H + i])
+#define KMPC_RS_ADDS(c, lm, um)                                                                                     \
+    if constexpr (CNT == 4)                                                                                         \
+        asm("s_nop 1" KMPC_RS_AD(c, lm, um, 0) KMPC_RS_AD(c, lm, um, 1) KMPC_RS_AD(c, lm, um, 2)                    \
+            KMPC_RS_AD(c, lm, um, 3)                                                                                \
+            : KMPC_RS_AD_OUT(0), KMPC_RS_AD_OUT(1), KMPC_RS_AD_OUT(2), KMPC_RS_AD_OUT(3)                            \
+            : KMPC_RS_AD_IN(0), KMPC_RS_AD_IN(1), KMPC_RS_AD_IN(2), KMPC_RS_AD_IN(3));                              \
+    else if constexpr (CNT == 2)                                                                                    \
+        asm("s_nop 1" KMPC_RS_AD(c, lm, um, 0) KMPC_RS_AD(c, lm, um, 1)                                             \
+            : KMPC_RS_AD_OUT(0), KMPC_RS_AD_OUT(1) : KMPC_RS_AD_IN(0), KMPC_RS_AD_IN(1));                           \
+    else                                                                                                            \
+        asm("s_nop 1" KMPC_RS_AD(c, lm, um, 0) : KMPC_RS_AD_OUT(0) : KMPC_RS_AD_IN(0))
+template <int D, int J0, int H, int M>
+__device__ __forceinline__ void rs_add_dpp_from(float (&v)[M]) {
+    constexpr int n = H - J0, CNT = n >= 4 ? 4 : (n >= 2 ? 2 : 1);
+    if constexpr (n > 0) {
+        if constexpr (D == 8) { KMPC_RS_ADDS("row_mirror", "0x3", "0xc"); }
+        else { KMPC_RS_ADDS("row_half_mirror", "0x5", "0xa"); }
+        rs_add_dpp_from<D, J0 + CNT, H>(v);
+    }
+}
+#undef KMPC_RS_ADDS
+#undef KMPC_RS_AD_IN
+#undef KMPC_RS_AD_OUT
+#undef KMPC_RS_AD
+// one level of that reduce-scatter with N slots left (a constant: the statements are sized by it)
+template <int M, int D, int N>
+__device__ __forceinline__ void rs_level_f32(float (&v)[M], int& slot) {
+    if constexpr (N > 1 && (D == 32 || D == 16)) {
+        constexpr int H = N / 2;
+        rs_swap_from<D, 0, H>(v);
+#pragma unroll
+        for (int j = 0; j < H; ++j) v[j] = v[j] + v[j + H];   // lower lanes: slot j, upper lanes: slot j + H
+        slot += (threadIdx.x & D) ? H : 0;
+    } else if constexpr (N > 1 && (D == 8 || D == 4)) {
+        constexpr int H = N / 2;
+        rs_add_dpp_from<D, 0, H>(v);
+        slot += (threadIdx.x & D) ? H : 0;
+    } else {
+        int n = N;
+        rs_level<M, D>(v, n, slot);
+    }
+}
+
 // Wave reduce-scatter of M = 2^k values (k <= 6): afterwards v[0] of lane l holds the wave total
 // of slot `slot` (returned); the 64/M lanes that agree in their high bits share a slot. Each
 // level sends the half it does not keep: ~M exchanges instead of 6M.
@@ -558,6 +680,16 @@ __device__ __forceinline__ void rs_level(T (&v)[M], int& n, int& slot) {
 template <int M, int GL = 64, class T>
 __device__ __forceinline__ int wave_reduce_scatter(T (&v)[M]) {
     static_assert(M <= GL, "one slot per lane at most");
+    if constexpr (KMPC_RS_ASM_F32 && KMPC_RS_BANK && GL == 64 && sizeof(T) == 4) {
+        int slot = 0;
+        rs_level_f32<M, 32, M>(v, slot);
+        rs_level_f32<M, 16, (M >> 1)>(v, slot);
+        rs_level_f32<M, 8, (M >> 2)>(v, slot);
+        rs_level_f32<M, 4, (M >> 3)>(v, slot);
+        rs_level_f32<M, 2, (M >> 4)>(v, slot);
+        rs_level_f32<M, 1, (M >> 5)>(v, slot);
+        return slot;
+    }
     int slot = 0, n = M;
     if constexpr (GL > 32) rs_level<M, 32>(v, n, slot);
     if constexpr (GL > 16) rs_level<M, 16>(v, n, slot);
@@ -1514,14 +1646,16 @@ __device__ __forceinline__ Real max_step(const TH& T, Shared<HM, NWM, typename T
 // (fmac_dpp_from) — no ds_write, no wave barrier, no uniform LDS reads, no cv[] array. The same
 // values in the same FMA order as the LDS form in factor(): bit-identical. J is a template
 // parameter (the row_newbcast lane is an immediate), hence the recursion instead of a loop.
-template <int J, int KM, class Real>
+template <int J, bool ONCE, int KM, class Real>
 __device__ __forceinline__ void ldl_steps_dpp(Real (&g)[KM], int r, bool& bad, Real& dinv) {
     static_assert(KM <= 32, "the column sits on two DPP rows");
     if constexpr (J < KM) {
         Real u = g[J];   // row r of the updated column J
         // (written by the previous step's asm FMACs, whose hazards the compiler does not pad: two
-        // wait states before the lane reads below — v_readlane, permlane16 swap, DPP — take it)
-        if constexpr (J > 0) asm("s_nop 1" : "+v"(u));
+        // wait states before the lane reads below — v_readlane, permlane16 swap, DPP — take it).
+        // g[J] is the first element of the previous step's first chunk: where that chunk has four
+        // or more elements (KM - J >= 4), its other FMACs are those wait states already.
+        if constexpr (J > 0 && (!ONCE || KM - J < 4)) asm("s_nop 1" : "+v"(u));
         Real ca = u, cb = u;
         if constexpr (KM > 16 && J + 1 < KM) swap16(ca, cb);
         const Real d = bcast(u, J);   // the pivot by v_readlane, as the LDS form (from the broadcast: slower)
@@ -1538,8 +1672,8 @@ __device__ __forceinline__ void ldl_steps_dpp(Real (&g)[KM], int r, bool& bad, R
         const Real l = (r > J) ? u * id : Real(0.0);  // L_rJ
         if (r == J) dinv = id;
         g[J] = l;
-        fmac_dpp_from<J + 1>(g, ca, cb, -l);   // g[k] = fma(-l, c_k, g[k]), k > J
-        ldl_steps_dpp<J + 1>(g, r, bad, dinv);
+        fmac_dpp_from<J + 1, ONCE>(g, ca, cb, -l);   // g[k] = fma(-l, c_k, g[k]), k > J
+        ldl_steps_dpp<J + 1, ONCE>(g, r, bad, dinv);
     }
 }
 
@@ -1829,7 +1963,7 @@ __device__ __forceinline__ bool factor(TH& T, Shared<HM, NWM, typename TH::real_
         }
         bool bad = false;
         Real dinv = Real(0.0);
-        if constexpr (DPPCOL) ldl_steps_dpp<0>(g, r, bad, dinv);   // the column in registers: all KM steps
+        if constexpr (DPPCOL) ldl_steps_dpp<0, fd_wait_once<Real>()>(g, r, bad, dinv);   // the column in registers: all KM steps
 #pragma unroll
         for (int j = DPPCOL ? KM : 0; j < KM; ++j) {
             const Real u = g[j];                    // row r of the updated column j
