@@ -49,6 +49,7 @@ bt_run_kernel(SolveArgs a0, BtRun r) {
             // 0.898 -> 0.913 ms per step, P = 1,024 1.92 -> 1.98 ms)
             const int b = blockIdx.x * WPB + grp<GL>();
             const int yb = b;
+            Handoff<HM, false> hand;
 #include "kmpc_ipm_body.inc"
         }
         __syncthreads();   // W0 (st.target) of every lane, and the solve's LDS, done
@@ -80,46 +81,38 @@ int launch_bt_run_one(const SolveArgs& a, int n_steps, int n_real, const float* 
     const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, double>();
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;
     hipLaunchKernelGGL((bt_run_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, 0>), dim3((a.B + WPB - 1) / WPB),
-                       dim3(GL == 64 ? 64 * ((a.N + 63) / 64) : 64), lds, stream, s, r);
+                       dim3(GL == 64 ? block_threads(a.N) : 64), lds, stream, s, r);
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
-// The packed shapes (launch_ipm_packed<HM>'s choice for case 7 with H = HM: N <= 32, 3 HM <= 32):
-// KMPC_ERR_UNSUPPORTED elsewhere (a ragged H runs the generic packed kernel: no persistent form).
+// launch_bt_run_one of a rung of the ladder (kmpc_solve_args.h). The persistent kernels exist for
+// the float64 constant case 7 with H = HM: KMPC_ERR_UNSUPPORTED on any other rung (a ragged H or
+// another case runs the generic kernel: no persistent form) and on the C3 rung, whose kernel is
+// launch_bt_run_c3's (kmpc_solve_c3.hip).
+template <class V, class... Args>
+int launch_bt_run_variant(V, const Args&... args) {
+    if constexpr (V::FL == 7 && V::EXACT && !V::C3)
+        return launch_bt_run_one<V::HM, V::MAXT, true, 7, V::CS, V::QL, V::GL>(args...);
+    else
+        return KMPC_ERR_UNSUPPORTED;
+}
+
+// The packed shapes: the rung launch_ipm_packed<HM> takes for the same batch.
 template <int HM>
 int launch_bt_run_packed(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
                          int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream) {
-    const int fl = case_of(!a.allow_short, a.c > 0.0 || a.tau > 0.0, a.tau > 0.0);
-    if (a.H != HM || a.N > 32 || 3 * HM > 32 || fl != 7) return KMPC_ERR_UNSUPPORTED;
-#define KMPC_BT_ARGS a, n_steps, n_real, yhat, realized, step0, S, c, weights, value, hist, stream
-    if constexpr (3 * HM <= 16) {
-        if (a.N <= 16) {
-            if (a.N <= KMPC_PACK_NS - 1) return launch_bt_run_one<HM, 64, true, 7, 4 * KMPC_PACK_NS, false, 16>(KMPC_BT_ARGS);
-            return launch_bt_run_one<HM, 64, true, 7, 64, false, 16>(KMPC_BT_ARGS);
-        }
-    }
-    if constexpr (3 * HM <= 32) return launch_bt_run_one<HM, 64, true, 7, 64, false, 32>(KMPC_BT_ARGS);
-#undef KMPC_BT_ARGS
-    return KMPC_ERR_UNSUPPORTED;
+    return visit_packed<HM>(a, [&](auto v) {
+        return launch_bt_run_variant(v, a, n_steps, n_real, yhat, realized, step0, S, c, weights, value, hist, stream);
+    });
 }
 
-// The constant-case shapes (launch_ipm_case<HM>'s choice for case 7: no short + cost + cap, H = HM,
-// N <= 256), except the C3 kernel's (kmpc_solve_c3.hip): KMPC_ERR_UNSUPPORTED elsewhere.
+// The constant-case shapes: the rung launch_ipm_case<HM> takes for the same batch.
 template <int HM>
 int launch_bt_run_case(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
                        int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream) {
-    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
-    const int fl = case_of(!a.allow_short, a.c > 0.0 || a.tau > 0.0, a.tau > 0.0);
-    if (a.H != HM || nt > 256 || fl != 7) return KMPC_ERR_UNSUPPORTED;
-#define KMPC_BT_ARGS a, n_steps, n_real, yhat, realized, step0, S, c, weights, value, hist, stream
-    if constexpr (HM == 10) {
-        if (nt == 128 && a.N < QL_CS) return KMPC_ERR_UNSUPPORTED;   // (the C3 unit's)
-        if (nt == 256 && a.N < QL_CS256) return launch_bt_run_one<HM, 256, true, 7, QL_CS256, true>(KMPC_BT_ARGS);
-    }
-    return nt <= 64 ? launch_bt_run_one<HM, 64, true, 7>(KMPC_BT_ARGS)
-                    : (nt <= 128 ? launch_bt_run_one<HM, 128, true, 7>(KMPC_BT_ARGS)
-                                 : launch_bt_run_one<HM, 256, true, 7>(KMPC_BT_ARGS));
-#undef KMPC_BT_ARGS
+    return visit_case<HM>(a, [&](auto v) {
+        return launch_bt_run_variant(v, a, n_steps, n_real, yhat, realized, step0, S, c, weights, value, hist, stream);
+    });
 }
 
 }  // namespace kmpc

@@ -51,6 +51,7 @@ bt_sweep_kernel(SolveArgs a0, BtRun r, BtSweep sw) {
             args.tau = tj;
             const int b = q;
             const int yb = p;
+            Handoff<HM, false> hand;
 #include "kmpc_ipm_body.inc"
         }
         __syncthreads();   // W0 (st.target) of every lane, and the solve's LDS, done
@@ -83,36 +84,28 @@ int launch_bt_sweep_one(const SolveArgs& a, const SweepLaunch& l, hipStream_t st
     const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, double>();
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;
     hipLaunchKernelGGL((bt_sweep_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, 0>), dim3((a.B + WPB - 1) / WPB),
-                       dim3(GL == 64 ? 64 * ((a.N + 63) / 64) : 64), lds, stream, s, r, sw);
+                       dim3(GL == 64 ? block_threads(a.N) : 64), lds, stream, s, r, sw);
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
-// the packed shapes, as launch_bt_run_packed<HM>
-template <int HM>
-int launch_bt_sweep_packed(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
-    if (a.H != HM || a.N > 32 || 3 * HM > 32) return KMPC_ERR_UNSUPPORTED;
-    if constexpr (3 * HM <= 16) {
-        if (a.N <= 16) {
-            if (a.N <= KMPC_PACK_NS - 1) return launch_bt_sweep_one<HM, 64, true, 7, 4 * KMPC_PACK_NS, false, 16>(a, l, stream);
-            return launch_bt_sweep_one<HM, 64, true, 7, 64, false, 16>(a, l, stream);
-        }
-    }
-    if constexpr (3 * HM <= 32) return launch_bt_sweep_one<HM, 64, true, 7, 64, false, 32>(a, l, stream);
-    return KMPC_ERR_UNSUPPORTED;
+// launch_bt_sweep_one of a rung of the ladder, as launch_bt_run_variant (the C3 rung's kernel is
+// launch_bt_sweep_c3's, kmpc_solve_c3sw.hip)
+template <class V>
+int launch_bt_sweep_variant(V, const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
+    if constexpr (V::FL == 7 && V::EXACT && !V::C3)
+        return launch_bt_sweep_one<V::HM, V::MAXT, true, 7, V::CS, V::QL, V::GL>(a, l, stream);
+    else
+        return KMPC_ERR_UNSUPPORTED;
 }
 
-// the constant-case shapes, as launch_bt_run_case<HM> (not the C3 kernel's: kmpc_solve_c3sw.hip)
+// the packed and the constant-case shapes, as launch_bt_run_packed<HM> and launch_bt_run_case<HM>
+template <int HM>
+int launch_bt_sweep_packed(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
+    return visit_packed<HM>(a, [&](auto v) { return launch_bt_sweep_variant(v, a, l, stream); });
+}
 template <int HM>
 int launch_bt_sweep_case(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
-    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
-    if (a.H != HM || nt > 256) return KMPC_ERR_UNSUPPORTED;
-    if constexpr (HM == 10) {
-        if (nt == 128 && a.N < QL_CS) return KMPC_ERR_UNSUPPORTED;   // (the C3 unit's)
-        if (nt == 256 && a.N < QL_CS256) return launch_bt_sweep_one<HM, 256, true, 7, QL_CS256, true>(a, l, stream);
-    }
-    return nt <= 64 ? launch_bt_sweep_one<HM, 64, true, 7>(a, l, stream)
-                    : (nt <= 128 ? launch_bt_sweep_one<HM, 128, true, 7>(a, l, stream)
-                                 : launch_bt_sweep_one<HM, 256, true, 7>(a, l, stream));
+    return visit_case<HM>(a, [&](auto v) { return launch_bt_sweep_variant(v, a, l, stream); });
 }
 
 }  // namespace kmpc

@@ -1,17 +1,22 @@
 // kmpc_ipm_body.inc — the body of one window's interior-point solve, textually included by
-// ipm_kernel (kmpc_solve_kernel.h) and by the path-persistent backtest kernel (kmpc_solve_c3.hip,
-// once per step). An include rather than a function: ipm_kernel's instruction stream stays exactly
+// ipm_kernel (kmpc_solve_kernel.h), by the path-persistent backtest kernels (kmpc_bt_run.h,
+// kmpc_bt_sweep.h: once per step) and, once per phase, by the fused mixed-precision kernel
+// (kmpc_solve_c3.hip). An include rather than a function: ipm_kernel's instruction stream stays exactly
 // what it was (a call boundary, even inlined, reshuffles this kernel's register allocation).
 // Names in scope at the include: HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX (template parameters; BOX
 // a constant false where the kernel has no box form), Real,
 // NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window: w_prev, outputs, warm record),
-// yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h).
+// yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h),
+// hand (Handoff<HM, ON>: the iterate the phases of the fused kernel pass on in registers; the empty
+// form elsewhere, where PH = 1 / 2 / 3 go through the window's record in args.warm).
+    // the iterate goes from phase to phase on chip (the fused kernel) or through args.warm
+    constexpr bool ON_CHIP = std::remove_reference_t<decltype(hand)>::ON;
     if constexpr (PH == 3) {   // the retry pass: only windows whose warm start did not end optimal
-#ifdef KMPC_FUSED_RETRY
-        if (!retry_flag) return;   // (the fused kernel: the float64 finish's verdict, workgroup-uniform)
-#else
-        if (reinterpret_cast<const int*>(args.warm + (size_t)b * args.warm_floats)[0] != 3) return;
-#endif
+        if constexpr (ON_CHIP) {
+            if (!hand.retry) return;   // (the float64 finish's verdict, workgroup-uniform)
+        } else {
+            if (reinterpret_cast<const int*>(args.warm + (size_t)b * args.warm_floats)[0] != 3) return;
+        }
     }
     // waves in the block: a compile-time constant up to 128 threads (the launchers use MAXT = 128
     // only for 128-thread blocks), so the reductions' per-wave slot loops need no run-time guards
@@ -114,70 +119,51 @@
             bool warm = false;
             const float* rec = nullptr;
             if constexpr (PH == 2) {
-#ifdef KMPC_REG_HANDOFF
-                warm = hand_flag;   // (the fused kernel: the float32 phase's iterate is in registers)
-#else
-                rec = args.warm + (size_t)b * args.warm_floats;
-                // (a wave-uniform flag: a scalar branch; unchanged in memory until the end)
-                warm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(rec)[0]) == 1;
-#endif
+                if constexpr (ON_CHIP) {
+                    warm = hand.flag;   // (the float32 phase's iterate is in registers)
+                } else {
+                    rec = args.warm + (size_t)b * args.warm_floats;
+                    // (a wave-uniform flag: a scalar branch; unchanged in memory until the end)
+                    warm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(rec)[0]) == 1;
+                }
             }
-#ifdef KMPC_REG_HANDOFF
-            if (warm) {   // promote the float32 iterate handed over in registers / LDS (exact)
-#if KMPC_REG_HANDOFF_ON == 2
-                const float* hl = reinterpret_cast<const float*>(kmpc_cold);   // [5][HM][CS] + [3][HM]
-                const int ln = hand_lane<CS>();
-#endif
+            if (warm) {   // promote the float32 iterate (exact): from registers, or from the record
+                if constexpr (ON_CHIP) {
 #pragma unroll
-                for (int t = 0; t < HM; ++t) {
-                    const bool on = T.act && t < H;
-#if KMPC_REG_HANDOFF_ON == 2
-                    T.w[t] = on ? (Real)hl[(0 * HM + t) * CS + ln] : Real(0.0);
-                    T.s[t] = on ? (Real)hl[(1 * HM + t) * CS + ln] : Real(0.0);
-                    T.l1[t] = on ? (Real)hl[(2 * HM + t) * CS + ln] : Real(0.0);
-                    T.l2[t] = on ? (Real)hl[(3 * HM + t) * CS + ln] : Real(0.0);
-                    T.l3[t] = on ? (Real)hl[(4 * HM + t) * CS + ln] : Real(0.0);
-#else
-                    T.w[t] = on ? (Real)hand_w[t] : Real(0.0);
-                    T.s[t] = on ? (Real)hand_s[t] : Real(0.0);
-                    T.l1[t] = on ? (Real)hand_l1[t] : Real(0.0);
-                    T.l2[t] = on ? (Real)hand_l2[t] : Real(0.0);
-                    T.l3[t] = on ? (Real)hand_l3[t] : Real(0.0);
-#endif
-                }
-                if (gvt<GL>() < HM) {
-                    const int t = gvt<GL>();
-                    const bool on = t < H;
-#if KMPC_REG_HANDOFF_ON == 2
-                    sh.z4[t] = on ? (Real)hl[5 * HM * CS + t] : Real(1.0);
-                    sh.l4[t] = on ? (Real)hl[5 * HM * CS + HM + t] : Real(0.0);
-                    sh.nu[t] = on ? (Real)hl[5 * HM * CS + 2 * HM + t] : Real(0.0);
-#else
-                    sh.z4[t] = on ? (Real)hand_z4 : Real(1.0);
-                    sh.l4[t] = on ? (Real)hand_l4 : Real(0.0);
-                    sh.nu[t] = on ? (Real)hand_nu : Real(0.0);
-#endif
-                }
-            } else
-#endif
-            if (warm) {
-                const float* st = rec + WARM_HEAD;
+                    for (int t = 0; t < HM; ++t) {
+                        const bool on = T.act && t < H;
+                        T.w[t] = on ? (Real)hand.w[t] : Real(0.0);
+                        T.s[t] = on ? (Real)hand.s[t] : Real(0.0);
+                        T.l1[t] = on ? (Real)hand.l1[t] : Real(0.0);
+                        T.l2[t] = on ? (Real)hand.l2[t] : Real(0.0);
+                        T.l3[t] = on ? (Real)hand.l3[t] : Real(0.0);
+                    }
+                    if (gvt<GL>() < HM) {
+                        const int t = gvt<GL>();
+                        const bool on = t < H;
+                        sh.z4[t] = on ? (Real)hand.z4 : Real(1.0);
+                        sh.l4[t] = on ? (Real)hand.l4 : Real(0.0);
+                        sh.nu[t] = on ? (Real)hand.nu : Real(0.0);
+                    }
+                } else {
+                    const float* st = rec + WARM_HEAD;
 #pragma unroll
-                for (int t = 0; t < HM; ++t) {
-                    const bool on = T.act && t < H;
-                    const int k = t * N + T.i;
-                    T.w[t] = on ? (Real)st[k] : Real(0.0);
-                    T.s[t] = on ? (Real)st[H * N + k] : Real(0.0);
-                    T.l1[t] = on ? (Real)st[2 * H * N + k] : Real(0.0);
-                    T.l2[t] = on ? (Real)st[3 * H * N + k] : Real(0.0);
-                    T.l3[t] = on ? (Real)st[4 * H * N + k] : Real(0.0);
-                }
-                if (gvt<GL>() < HM) {
-                    const int t = gvt<GL>();
-                    const bool on = t < H;
-                    sh.z4[t] = on ? (Real)st[5 * H * N + t] : Real(1.0);
-                    sh.l4[t] = on ? (Real)st[5 * H * N + H + t] : Real(0.0);
-                    sh.nu[t] = on ? (Real)st[5 * H * N + 2 * H + t] : Real(0.0);
+                    for (int t = 0; t < HM; ++t) {
+                        const bool on = T.act && t < H;
+                        const int k = t * N + T.i;
+                        T.w[t] = on ? (Real)st[k] : Real(0.0);
+                        T.s[t] = on ? (Real)st[H * N + k] : Real(0.0);
+                        T.l1[t] = on ? (Real)st[2 * H * N + k] : Real(0.0);
+                        T.l2[t] = on ? (Real)st[3 * H * N + k] : Real(0.0);
+                        T.l3[t] = on ? (Real)st[4 * H * N + k] : Real(0.0);
+                    }
+                    if (gvt<GL>() < HM) {
+                        const int t = gvt<GL>();
+                        const bool on = t < H;
+                        sh.z4[t] = on ? (Real)st[5 * H * N + t] : Real(1.0);
+                        sh.l4[t] = on ? (Real)st[5 * H * N + H + t] : Real(0.0);
+                        sh.nu[t] = on ? (Real)st[5 * H * N + 2 * H + t] : Real(0.0);
+                    }
                 }
             } else {
 #pragma unroll
@@ -338,9 +324,8 @@
                     // reloads it piecemeal inside the iteration (107 -> 54 spilled dwords; C3 solve
                     // +6%, N = 250 +16%, measured r02). The empty asm takes the array's address,
                     // so it stays in memory and the loads are not forwarded from the stores.
-                    // (the float32 phase has registers to spare at one wave per SIMD: no parking
-                    // unless KMPC_F32_PARK)
-                    constexpr bool PARK = sizeof(Real) == 8 ? KMPC_F64_PARK : KMPC_F32_PARK;
+                    // (the float32 phase has registers to spare at one wave per SIMD: no parking)
+                    constexpr bool PARK = sizeof(Real) == 8;
                     Real park[2 * HM];
 #pragma unroll
                     for (int t = 0; t < HM; ++t) { park[t] = T.w[t]; park[HM + t] = T.s[t]; }
@@ -448,52 +433,29 @@
         }
     }
     if constexpr (PH == 1) {
-        // the window's warm record: the iterate at the handoff (float32, [5][H][N] + [3][H]),
-        // or a cold mark (special cases, a float breakdown: the float64 phase starts over)
+        // the iterate at the handoff goes on: in this lane's registers in the fused kernel, else to
+        // the window's warm record (float32, [5][H][N] + [3][H]). The record's header goes out in
+        // both: warm, or a cold mark (special cases, a float breakdown: the float64 finish starts
+        // over), and the iterations spent
         float* rec = args.warm + (size_t)b * args.warm_floats;
-#ifdef KMPC_REG_HANDOFF
-        // the fused kernel: the iterate stays in this lane's registers for the float64 finish (no
-        // 20 KB record through memory); the header below still goes out (the retry pass reads it)
-        hand_flag = handoff;
-        if (handoff) {
-#if KMPC_REG_HANDOFF_ON == 2
-            // into the float64 finish's cold-array LDS (unused by this phase: its cold arrays are
-            // in registers), read back before the finish's first factor() writes it
-            float* hl = reinterpret_cast<float*>(kmpc_cold);
-            const int ln = hand_lane<CS>();
+        if constexpr (ON_CHIP) {
+            hand.flag = handoff;
+            if (handoff) {
 #pragma unroll
-            for (int t = 0; t < HM; ++t) {
-                hl[(0 * HM + t) * CS + ln] = T.w[t];
-                hl[(1 * HM + t) * CS + ln] = T.s[t];
-                hl[(2 * HM + t) * CS + ln] = T.l1[t];
-                hl[(3 * HM + t) * CS + ln] = T.l2[t];
-                hl[(4 * HM + t) * CS + ln] = T.l3[t];
+                for (int t = 0; t < HM; ++t) {
+                    hand.w[t] = T.w[t];
+                    hand.s[t] = T.s[t];
+                    hand.l1[t] = T.l1[t];
+                    hand.l2[t] = T.l2[t];
+                    hand.l3[t] = T.l3[t];
+                }
+                if (gvt<GL>() < HM) {
+                    hand.z4 = sh.z4[gvt<GL>()];
+                    hand.l4 = sh.l4[gvt<GL>()];
+                    hand.nu = sh.nu[gvt<GL>()];
+                }
             }
-            if (gvt<GL>() < HM) {
-                hl[5 * HM * CS + gvt<GL>()] = sh.z4[gvt<GL>()];
-                hl[5 * HM * CS + HM + gvt<GL>()] = sh.l4[gvt<GL>()];
-                hl[5 * HM * CS + 2 * HM + gvt<GL>()] = sh.nu[gvt<GL>()];
-            }
-#else
-#pragma unroll
-            for (int t = 0; t < HM; ++t) {
-                hand_w[t] = T.w[t];
-                hand_s[t] = T.s[t];
-                hand_l1[t] = T.l1[t];
-                hand_l2[t] = T.l2[t];
-                hand_l3[t] = T.l3[t];
-            }
-            if (gvt<GL>() < HM) {
-                hand_z4 = sh.z4[gvt<GL>()];
-                hand_l4 = sh.l4[gvt<GL>()];
-                hand_nu = sh.nu[gvt<GL>()];
-            }
-#endif
-        }
-        if (false) {
-#else
-        if (handoff) {
-#endif
+        } else if (handoff) {
             float* st = rec + WARM_HEAD;
 #pragma unroll
             for (int t = 0; t < HM; ++t) {
@@ -521,10 +483,8 @@
         return;
     }
     __syncthreads();
-#ifdef KMPC_FUSED_RETRY
     // (thread 0's test below, by every thread: the status comes from workgroup-wide reductions)
-    if constexpr (PH == 2) retry_flag = hand_flag && status != KMPC_STATUS_OPTIMAL;
-#endif
+    if constexpr (PH == 2 && ON_CHIP) hand.retry = hand.flag && status != KMPC_STATUS_OPTIMAL;
     // ---- outputs: W was written by record_best; fallback (mpc.py:113-115) otherwise ----
     const bool ok = status == KMPC_STATUS_OPTIMAL || status == KMPC_STATUS_OPTIMAL_INACCURATE;
     if (!ok && T.act) {

@@ -38,7 +38,6 @@
 
 namespace kmpc {
 
-constexpr int WAVE = 64;
 #ifdef KMPC_STATS
 __device__ unsigned long long g_stats[2];   // dev builds only: refinement steps, Newton solves
 __device__ unsigned long long g_phase[16];  // dev builds only: s_memtime cycles per solver phase
@@ -94,13 +93,6 @@ struct PhaseClock {};
 // (tools/ab_mixed.sh); two waves per SIMD without the LDS change: no difference
 #ifndef KMPC_F32_WPE
 #define KMPC_F32_WPE 1
-#endif
-// dev A/B: park w, s in scratch across the float32 phase's Newton solves as the float64 kernel does
-#ifndef KMPC_F32_PARK
-#define KMPC_F32_PARK 0
-#endif
-#ifndef KMPC_F64_PARK   // dev A/B: 0 keeps w, s in registers across the float64 Newton solves
-#define KMPC_F64_PARK 1
 #endif
 #ifndef KMPC_REFINE_RTOL
 #define KMPC_REFINE_RTOL 1e-5
@@ -831,7 +823,6 @@ struct Case<-1> {
     bool hw, hs, ht;
     __device__ __forceinline__ void set_case(bool a, bool b, bool c) { hw = a; hs = b; ht = c; }
 };
-__host__ __device__ constexpr int case_of(bool hw, bool hs, bool ht) { return (hw ? 1 : 0) | (hs ? 2 : 0) | (ht ? 4 : 0); }
 
 // State of the box case (BOX: the per-asset position limit w <= u, one more barrier on w with slack
 // u - w taken from the iterate): the multiplier l5, and two cold arrays, the slack
@@ -2041,14 +2032,34 @@ __device__ __forceinline__ Real record_best(const TH& T, Reducer<HM, NWM, TH::GL
 // GL < 64: 64 / GL windows packed per one-wave block (lane groups; MAXT = 64, N <= GL).
 // PH (mixed precision): 0 = the whole solve in float64; 1 = the float32 warm-start
 // phase — the same iteration in float32 until mu <= args.mu_handoff, then the iterate (w, s, l1..l3,
-// z4, l4, nu) goes to the window's record in args.warm and the kernel exits (no outputs); a window
-// it cannot hand over (special cases, a float breakdown) is marked cold; 2 = the float64 solve,
-// started from the window's record when it is warm (from the usual initial point when cold).
+// z4, l4, nu) goes to the float64 finish — through the window's record in args.warm here, in
+// registers (hand, below) in the fused kernel of kmpc_solve_c3.hip — and the phase ends (no
+// outputs); a window it cannot hand over (special cases, a float breakdown) is marked cold; 2 = the
+// float64 finish, started from that iterate when the window is warm (from the usual initial point
+// when cold); 3 = the retry of a warm start that did not end optimal, from the usual initial point.
 // BOX: the box case, a per-asset position limit w <= args.max_weight (kmpc_solve_box; float64,
 // whole-wave windows, the generic constraint case only).
 // The window body (kmpc_ipm_body.inc) reads BOX by name: the kernels that include it without a box
 // form (the mixed, path-persistent and sweep kernels) see this constant, ipm_kernel its own parameter.
 constexpr bool BOX = false;
+// ... and the iterate handed from phase to phase on chip by the name hand: ipm_kernel and the
+// backtest kernels declare the empty form (Handoff::ON false: PH = 1 / 2 / 3 go through args.warm),
+// the fused kernel the full one. The full form refers to separate locals of that kernel: as
+// members of one aggregate they moved its register allocation (87 -> 83 spilled VGPRs, 16 B more
+// scratch); as separate locals its assembly equals the earlier form's with named locals and macro
+// guards (profiles/dispatch_refactor.md).
+template <int HM, bool ON_>
+struct Handoff {
+    static constexpr bool ON = ON_;
+};
+template <int HM>
+struct Handoff<HM, true> {
+    static constexpr bool ON = true;
+    float (&w)[HM], (&s)[HM], (&l1)[HM], (&l2)[HM], (&l3)[HM];   // this lane's asset
+    float &z4, &l4, &nu;                                         // this lane's period (lanes below HM)
+    bool& flag;    // the float32 phase handed its iterate over (else a cold start)
+    bool& retry;   // the warm start did not end optimal: the retry pass runs
+};
 template <int HM, int MAXT, bool EXACT, int FL = -1, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0, bool BOX = false>
 __global__ void __launch_bounds__(MAXT)
 __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM ? 2 : 1)))) ipm_kernel(SolveArgs args) {
@@ -2069,33 +2080,33 @@ __attribute__((amdgpu_waves_per_eu(PH == 1 ? KMPC_F32_WPE : (HM <= KMPC_WPE2_HM 
     const int b = blockIdx.x * WPB + grp<GL>();
     if (b >= args.B) return;   // (whole groups of the last block)
     const int yb = b;
+    Handoff<HM, false> hand;
 #include "kmpc_ipm_body.inc"
 }
 
 template <int HM, int MAXT, bool EXACT, int FL, int CS = MAXT, bool QL = false, int GL = 64, int PH = 0, bool BOX = false>
-int launch_one(const SolveArgs& a, int nt, hipStream_t stream) {
+int launch_one(const SolveArgs& a, hipStream_t stream) {
     const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, std::conditional_t<PH == 1, float, double>, BOX>();
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;
-    hipLaunchKernelGGL((ipm_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX>), dim3((a.B + WPB - 1) / WPB), dim3(nt), lds, stream, a);
+    hipLaunchKernelGGL((ipm_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX>), dim3((a.B + WPB - 1) / WPB),
+                       dim3(GL == 64 ? block_threads(a.N) : 64), lds, stream, a);
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
-
-constexpr int QL_CS256 = 216;  // ... and of the 256-thread one
 
 // Generic launcher (constraint case read at run time): one workgroup of 64 * ceil(N / 64) threads
 // per window. The 64-thread variant sizes its LDS for one wave, so four one-wave windows share a
 // CU (the 128-thread variant's LDS admits two windows per CU).
 template <int HM>
 int launch_ipm(const SolveArgs& a, hipStream_t stream) {
-    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
+    const int nt = block_threads(a.N);
     const bool exact = a.H == HM;
-    if (nt <= 64) return exact ? launch_one<HM, 64, true, -1>(a, nt, stream) : launch_one<HM, 64, false, -1>(a, nt, stream);
+    if (nt <= 64) return exact ? launch_one<HM, 64, true, -1>(a, stream) : launch_one<HM, 64, false, -1>(a, stream);
     if constexpr (HM == 10)   // QL variant (LDL^T arrays in LDS): 40 -> 0 spilled dwords
         if (nt == 128 && a.N < QL_CS)
-            return exact ? launch_one<HM, 128, true, -1, QL_CS, true>(a, nt, stream)
-                         : launch_one<HM, 128, false, -1, QL_CS, true>(a, nt, stream);
-    if (nt <= 128) return exact ? launch_one<HM, 128, true, -1>(a, nt, stream) : launch_one<HM, 128, false, -1>(a, nt, stream);
-    if (nt <= 256) return exact ? launch_one<HM, 256, true, -1>(a, nt, stream) : launch_one<HM, 256, false, -1>(a, nt, stream);
+            return exact ? launch_one<HM, 128, true, -1, QL_CS, true>(a, stream)
+                         : launch_one<HM, 128, false, -1, QL_CS, true>(a, stream);
+    if (nt <= 128) return exact ? launch_one<HM, 128, true, -1>(a, stream) : launch_one<HM, 128, false, -1>(a, stream);
+    if (nt <= 256) return exact ? launch_one<HM, 256, true, -1>(a, stream) : launch_one<HM, 256, false, -1>(a, stream);
     // past 256 assets a window's state does not fit the registers of one block: kmpc_solve_big.h
     return KMPC_ERR_UNSUPPORTED;
 }
@@ -2113,77 +2124,38 @@ int launch_ipm(const SolveArgs& a, hipStream_t stream) {
 #endif
 template <int HM>
 int launch_ipm_box(const SolveArgs& a, hipStream_t stream) {
-    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
+    const int nt = block_threads(a.N);
     if (a.H > HM || nt > 256) return KMPC_ERR_UNSUPPORTED;
 #if KMPC_BOX_QLCS
     if constexpr (HM == 10)
-        if (nt == 128 && a.N < QL_CS) return launch_one<HM, 128, false, -1, QL_CS, false, 64, 0, true>(a, nt, stream);
+        if (nt == 128 && a.N < QL_CS) return launch_one<HM, 128, false, -1, QL_CS, false, 64, 0, true>(a, stream);
 #endif
-    if (nt <= 64) return launch_one<HM, 64, false, -1, 64, false, 64, 0, true>(a, nt, stream);
-    if (nt <= 128) return launch_one<HM, 128, false, -1, 128, false, 64, 0, true>(a, nt, stream);
-    return launch_one<HM, 256, false, -1, 256, false, 64, 0, true>(a, nt, stream);
+    if (nt <= 64) return launch_one<HM, 64, false, -1, 64, false, 64, 0, true>(a, stream);
+    if (nt <= 128) return launch_one<HM, 128, false, -1, 128, false, 64, 0, true>(a, stream);
+    return launch_one<HM, 256, false, -1, 256, false, 64, 0, true>(a, stream);
 }
 
-// Constant-case launcher (H == HM, N <= 128; case 7 up to 256): the constraint case is a template argument, so every
-// predicate on it folds away. Cases: 7 = no short + cost + cap (the benchmark's), 1 = no short
-// only (c = tau = 0: the simplex program of BASELINE configs[1]). Returns KMPC_ERR_UNSUPPORTED for
-// any other case (the caller then uses launch_ipm).
+// launch_one of a rung of the ladder (kmpc_solve_args.h)
+template <class V>
+int launch_variant(V, const SolveArgs& a, hipStream_t stream) {
+    return launch_one<V::HM, V::MAXT, V::EXACT, V::FL, V::CS, V::QL, V::GL>(a, stream);
+}
+
+// Constant-case launcher: the rungs of visit_case<HM>, the C3 rung's kernel in its own unit.
+// KMPC_ERR_UNSUPPORTED where the ladder has no rung (the caller then uses launch_ipm).
 template <int HM>
 int launch_ipm_case(const SolveArgs& a, hipStream_t stream) {
-    const int nt = WAVE * ((a.N + WAVE - 1) / WAVE);
-    const int fl = case_of(!a.allow_short, a.c > 0.0 || a.tau > 0.0, a.tau > 0.0);
-    if (a.H != HM || nt > 256) return KMPC_ERR_UNSUPPORTED;
-    if (fl == 7) {
-        // N <= 103 at H = 10 (BASELINE configs[2..3]: N = 100): the per-asset LDL^T arrays (iDd, Lr)
-        // join the cold arrays in LDS with a 104-lane stride (two windows per CU still fit):
-        // 40 VGPRs of live state less, 132 -> 107 spilled dwords, C3 solve +4.5% (measured r02)
-        if constexpr (HM == 10) {
-            if (nt == 128 && a.N < QL_CS) return launch_ipm_c3(a, stream);
-            // 256-thread windows (one per CU): the 8 cold arrays at a 216-lane stride fit 160 KB
-            // (151 -> 108 spilled dwords; N = 200 +6.7%, measured r02)
-            if (nt == 256 && a.N < QL_CS256) return launch_one<HM, 256, true, 7, QL_CS256, true>(a, nt, stream);
-        }
-        return nt <= 64 ? launch_one<HM, 64, true, 7>(a, nt, stream)
-                        : (nt <= 128 ? launch_one<HM, 128, true, 7>(a, nt, stream) : launch_one<HM, 256, true, 7>(a, nt, stream));
-    }
-    if (nt > 128) return KMPC_ERR_UNSUPPORTED;
-    if (fl == 1) return nt <= 64 ? launch_one<HM, 64, true, 1>(a, nt, stream) : launch_one<HM, 128, true, 1>(a, nt, stream);
-    return KMPC_ERR_UNSUPPORTED;
+    return visit_case<HM>(a, [&](auto v) -> int {
+        if constexpr (decltype(v)::C3) return launch_ipm_c3(a, stream);
+        else return launch_variant(v, a, stream);
+    });
 }
 
-}  // namespace kmpc
-
-namespace kmpc {
-
-#ifndef KMPC_PACK_NS   // cold-array slots per 16-lane window of the packed N <= 10 launch
-#define KMPC_PACK_NS 11
-#endif
-// Packed launcher: windows of N <= 32 assets (3 H <= GL) run 64 / GL per one-wave block, each on
-// its own lane group (GL = 16 for N <= 16 when 3 HM <= 16, else 32). Constant-case kernels for
-// H == HM in the two common cases (FL = 7, FL = 1), the generic kernel otherwise. Returns
-// KMPC_ERR_UNSUPPORTED outside that range (the caller then uses one window per wave).
+// Packed launcher: the rungs of visit_packed<HM>. KMPC_ERR_UNSUPPORTED outside N <= 32, 3 HM <= 32
+// (the caller then uses one window per wave).
 template <int HM>
 int launch_ipm_packed(const SolveArgs& a, hipStream_t stream) {
-    if (a.H > HM || a.N > 32 || 3 * HM > 32) return KMPC_ERR_UNSUPPORTED;
-    const int fl = case_of(!a.allow_short, a.c > 0.0 || a.tau > 0.0, a.tau > 0.0);
-    const bool exact = a.H == HM;
-    if constexpr (3 * HM <= 16) {
-        if (a.N <= 16) {
-            // N <= 10 (BASELINE configs[0]): the cold arrays at 11 slots per window instead of 16
-            // (44 per block): 29 -> 24 KB of LDS per block, six blocks per CU instead of five
-            if (exact && fl == 7 && a.N <= KMPC_PACK_NS - 1)
-                return launch_one<HM, 64, true, 7, 4 * KMPC_PACK_NS, false, 16>(a, 64, stream);
-            if (exact && fl == 7) return launch_one<HM, 64, true, 7, 64, false, 16>(a, 64, stream);
-            if (exact && fl == 1) return launch_one<HM, 64, true, 1, 64, false, 16>(a, 64, stream);
-            return launch_one<HM, 64, false, -1, 64, false, 16>(a, 64, stream);
-        }
-    }
-    if constexpr (3 * HM <= 32) {
-        if (exact && fl == 7) return launch_one<HM, 64, true, 7, 64, false, 32>(a, 64, stream);
-        if (exact && fl == 1) return launch_one<HM, 64, true, 1, 64, false, 32>(a, 64, stream);
-        return launch_one<HM, 64, false, -1, 64, false, 32>(a, 64, stream);
-    }
-    return KMPC_ERR_UNSUPPORTED;
+    return visit_packed<HM>(a, [&](auto v) -> int { return launch_variant(v, a, stream); });
 }
 
 }  // namespace kmpc

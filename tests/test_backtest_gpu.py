@@ -200,6 +200,9 @@ def test_lockstep_path_groups_on_streams_equal_one_group(P, groups):
 @pytest.mark.parametrize("P,T,chunk,N,H,path", [(64, 22, None, 100, 10, 0), (61, 19, 128, 100, 10, 0),
                                                   (24, 14, None, 100, 5, 0), (20, 15, None, 50, 10, 0),
                                                   (16, 14, None, 150, 10, 0), (12, 12, None, 200, 5, 0),
+                                                  # H = 10 past the LDS-array strides: the plain 128-thread
+                                                  # (N >= 104) and 256-thread (N >= 216) kernels, 2 steps
+                                                  (4, 12, None, 120, 10, 0), (4, 12, None, 230, 10, 0),
                                                   # packed (N <= 32; KMPC_PATH_REGISTER packs at any batch
                                                   # size): one path per lane group
                                                   (64, 30, None, 10, 5, 1), (61, 14, 80, 10, 5, 1),
@@ -213,7 +216,8 @@ def test_persistent_backtest_equals_lockstep_loop(P, T, chunk, N, H, path, monke
     lock-step loop (one kmpc_solve over the P windows + one kmpc_backtest_step per step): the same
     window solve and bookkeeping code, so histories, weights and metrics are bit-identical. P = 61
     with 2 steps per rollout chunk: several launches, each resuming the paths' state. The other
-    shapes: the constant-case kernels' persistent forms (64-, 128- and 256-thread windows, H = 5),
+    shapes: the constant-case kernels' persistent forms (64-, 128- and 256-thread windows, H = 5, and
+    at H = 10 the plain 128- and 256-thread ones past the C3 and 216-lane strides: N = 120, 230),
     the packed kernels' (N <= 32: 16-lane groups with 11 or 16 cold slots, 32-lane groups, H = 2 /
     5 / 10; one path per lane group, the bookkeeping's sums as group butterflies — the lock-step
     kernel's order — with ragged last blocks: P = 61, 22, 21, 19, 9), and N <= 32 under AUTO below

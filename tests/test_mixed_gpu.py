@@ -1,12 +1,12 @@
 """GPU parity of the mixed-precision solve (kmpc_solve_desc.precision = AUTO at the C3 shape): a
-float32 interior-point phase (ipm_kernel PH = 1) hands its iterate over at mu <= mu_handoff, and the
-float64 kernel (PH = 2) finishes from it under the same stopping and status rules as the float64-only
+float32 interior-point phase (the window body with PH = 1) hands its iterate over at mu <= mu_handoff, and the
+float64 finish (PH = 2, the same launch) goes on from it under the same stopping and status rules as the float64-only
 solve (precision = F64). The answer's bar is the float64 solve's (test_solver_gpu.py): objective
 within 1e-6 + 1e-5 |f*| of the long-double oracle, W[0] within 1e-3 (c > 0: unique optimum),
 feasibility to 1e-8 — the float32 phase only chooses the starting point of the float64 iteration.
 
 Also BASELINE configs[3]'s per-rank workload (131,072 windows per rank at N = 8) on one
-GPU, a batch past 131,072 windows (the r05 warm-record chunk) and one past 2^22 (two launches).
+GPU, a batch past 131,072 windows (where the three-launch form chunks the batch) and one past 2^22 (two launches).
 """
 import numpy as np
 import pytest
@@ -87,8 +87,10 @@ def test_mixed_handoff_threshold_keeps_parity(mu_handoff):
 
 
 def test_warm_records_chunk_boundary():
-    """Past 131,072 windows (the r05 record chunk; one launch with the 64 B header): windows on
-    either side of the boundary equal the same windows solved alone, bit for bit."""
+    """Past 131,072 windows in one launch (one 64 B header per window; the three-launch form of the
+    mixed solve, which the default build does not run, goes in chunks of 131,072 windows through a
+    20 KB record each): windows on either side of that boundary equal the same windows solved alone,
+    bit for bit."""
     rng = np.random.default_rng(3)
     B, N, H = 131072 + 96, 100, 10
     wp = rng.dirichlet(np.ones(N), B)

@@ -77,6 +77,7 @@ def _runs(N, H, path, chunk):
     (100, 5, 0, None),                       # 128 threads
     (150, 10, 0, None),                      # 256 threads, LDL^T arrays in LDS
     (200, 5, 0, None),                       # 256 threads
+    (120, 10, 0, None), (230, 10, 0, None),  # H = 10 past the LDS-array strides: plain 128 and 256 threads
     (100, 10, 0, None),                      # the C3 unit
     (10, 5, 1, 9), (100, 10, 0, 9)])         # several launches, each resuming the state
 def test_sweep_equals_existing_engine_per_config(N, H, path, chunk):
