@@ -218,6 +218,66 @@ LOCKSTEP_GROUPS = 3
 LOCKSTEP_GROUPS_MAX_P = 1024
 
 
+def _prepare_paths(km: DeviceKoopman, obs, realized, config: BacktestConfig, mean, std, n_rows: Optional[int]):
+    """The P paths of a device backtest (run_backtest_lockstep's obs, realized, mean, std, n_rows):
+    x [P, T, obs] and r [P, T, N] on the device, the test indices of the steps (a list, and steps_t
+    on the device), S = len(steps), and per step the [P, obs] rows of test index t, contiguous
+    (xt [T, P, obs]: one copy up front instead of one gather per step), the realized returns likewise
+    (rt [T, P, N]: step t reads row t + 1) and the rollout's de-standardisation m, sd."""
+    from types import SimpleNamespace
+    dev = km.device
+    x = torch.as_tensor(obs).to(dev, torch.float32)
+    r = torch.as_tensor(realized).to(dev, torch.float32).contiguous()
+    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2]:
+        raise ValueError("obs must be [P, T, obs] and realized [P, T, N]")
+    P, T, N = r.shape
+    n_rows = T if n_rows is None else int(n_rows)
+    steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
+    m, sd = km._stats(mean, std, N)
+    return SimpleNamespace(x=x, r=r, P=P, T=T, N=N, n_rows=n_rows, steps=steps, S=len(steps),
+                           xt=x.transpose(0, 1).contiguous(), rt=r.transpose(0, 1).contiguous(),
+                           steps_t=torch.as_tensor(steps, dtype=torch.long, device=dev), m=m, sd=sd)
+
+
+def _run_persistent(km: DeviceKoopman, pp, mpc_config: MPCConfig, entry, n_items: int, w, value, hist,
+                    metrics) -> bool:
+    """Every step of the paths pp (_prepare_paths) in launches of a path-persistent entry point, one
+    per rollout chunk of PREROLL_CHUNK // P steps, then the metrics: n_items work items (P paths, or
+    configs x paths) with their state in w, value, hist. entry(sdesc, k0, n, ...) -> the code of
+    kmpc_backtest_run or kmpc_backtest_sweep, given the arguments the two share: from the solve
+    descriptor, then the step range on. False (nothing run) where the C ABI has no persistent kernel
+    for the shape, and with a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it
+    and the persistent kernel has no box form — the lock-step loop's solves go through kmpc_solve_box."""
+    P, T, N, S, H, dev = pp.P, pp.T, pp.N, pp.S, int(mpc_config.horizon), km.device
+    if _box_limit(mpc_config, N):
+        return False
+    sdesc = _solve_desc(n_items, N, H, mpc_config, False)
+    target = torch.empty((n_items, N), dtype=torch.float64, device=dev)
+    status = torch.empty((n_items,), dtype=torch.int32, device=dev)
+    objv = torch.empty((n_items,), dtype=torch.float64, device=dev)
+    sh = _lib.stream_handle(dev)
+
+    def call(k0, n, y, rr, n_real):
+        return entry(ctypes.byref(sdesc), k0, n, y, rr, n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(),
+                     target.data_ptr(), status.data_ptr(), objv.data_ptr(), sh)
+
+    rc = call(0, 0, None, None, 0)   # (shape check only)
+    if rc == _lib.KMPC_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc)
+    sc = max(1, PREROLL_CHUNK // P)          # steps per batched rollout
+    for k0 in range(0, S, sc):
+        n = min(sc, S - k0)
+        y = km.rollout(pp.xt[pp.steps_t[k0:k0 + n]].reshape(n * P, -1), pp.m, pp.sd, H, N).contiguous()
+        tn = pp.steps_t[k0:k0 + n] + 1
+        n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
+        rr = pp.rt[tn[:n_real]].contiguous() if n_real else None
+        _lib.check(call(k0, n, y.data_ptr(), rr.data_ptr() if rr is not None else None, n_real))
+    dm = _lib.BacktestDesc(n_items, N, max(S, 1), 0.0)
+    _lib.check(_lib.load().kmpc_backtest_metrics(ctypes.byref(dm), hist.data_ptr(), metrics.data_ptr(), sh))
+    return True
+
+
 def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: BacktestConfig,
                           mean, std, n_rows: Optional[int] = None, graph: bool = False,
                           prerollout: bool = True, groups: Optional[int] = None,
@@ -259,19 +319,9 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
     """
     km = strategy.device_model()
     dev = km.device
-    x = torch.as_tensor(obs).to(dev, torch.float32)
-    r = torch.as_tensor(realized).to(dev, torch.float32).contiguous()
-    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2]:
-        raise ValueError("obs must be [P, T, obs] and realized [P, T, N]")
-    P, T, N = r.shape
-    n_rows = T if n_rows is None else int(n_rows)
-    steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
-    S = len(steps)
-    # per step the [P, obs] rows of test index t, contiguous ([T, P, obs]: one copy up front instead
-    # of one gather per step), and the realized returns of t + 1
-    xt = x.transpose(0, 1).contiguous()
-    rt = r.transpose(0, 1).contiguous()
-    m, sd = km._stats(mean, std, N)
+    pp = _prepare_paths(km, obs, realized, config, mean, std, n_rows)
+    P, T, N, steps, S = pp.P, pp.T, pp.N, pp.steps, pp.S
+    xt, rt, steps_t, m, sd = pp.xt, pp.rt, pp.steps_t, pp.m, pp.sd
     w = torch.full((P, N), 1.0 / N, dtype=torch.float64, device=dev)       # backtest.py:161
     value = torch.full((P,), float(config.initial_capital), dtype=torch.float64, device=dev)
     hist = torch.empty((P, max(S, 1), 4), dtype=torch.float64, device=dev)
@@ -281,7 +331,6 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
 
     H = int(strategy.mpc_config.horizon)
     sc = max(1, PREROLL_CHUNK // P)          # steps per batched rollout
-    steps_t = torch.as_tensor(steps, dtype=torch.long, device=dev)
     groups_arg = groups
     if groups is None:
         groups = LOCKSTEP_GROUPS if (prerollout and not graph and P <= LOCKSTEP_GROUPS_MAX_P) else 1
@@ -296,40 +345,16 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
         raise ValueError("persistent needs prerollout=True and graph=False")
 
     def run_persistent() -> bool:
-        """Every step of every path in kmpc_backtest_run launches (one per rollout chunk of sc steps):
-        False (nothing run) where the C ABI has no persistent kernel for this shape."""
-        if _box_limit(strategy.mpc_config, N):
-            # a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it and the
-            # persistent kernel has no box form — the loop's solves go through kmpc_solve_box
-            if explicit:
-                raise ValueError("persistent=True: no persistent backtest kernel for this shape")
-            return False
-        sdesc = _solve_desc(P, N, H, strategy.mpc_config, False)
-        target = torch.empty((P, N), dtype=torch.float64, device=dev)
-        status = torch.empty((P,), dtype=torch.int32, device=dev)
-        objv = torch.empty((P,), dtype=torch.float64, device=dev)
-        sh = _lib.stream_handle(dev)
+        """Every step of every path in kmpc_backtest_run launches (_run_persistent): False (nothing
+        run) where there is no persistent kernel for this shape."""
+        def entry(*a):
+            return L.kmpc_backtest_run(ctypes.byref(d), *a)
 
-        def call(k0, n, y, rr, n_real):
-            return L.kmpc_backtest_run(ctypes.byref(d), ctypes.byref(sdesc), k0, n, y, rr, n_real, w.data_ptr(),
-                                       value.data_ptr(), hist.data_ptr(), target.data_ptr(), status.data_ptr(),
-                                       objv.data_ptr(), sh)
-
-        rc = call(0, 0, None, None, 0)   # (shape check only)
-        if rc == _lib.KMPC_ERR_UNSUPPORTED:
-            if explicit:
-                raise ValueError("persistent=True: no persistent backtest kernel for this shape")
-            return False
-        _lib.check(rc)
-        for k0 in range(0, S, sc):
-            n = min(sc, S - k0)
-            y = km.rollout(xt[steps_t[k0:k0 + n]].reshape(n * P, -1), m, sd, H, N).contiguous()
-            tn = steps_t[k0:k0 + n] + 1
-            n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
-            rr = rt[tn[:n_real]].contiguous() if n_real else None
-            _lib.check(call(k0, n, y.data_ptr(), rr.data_ptr() if rr is not None else None, n_real))
-        _lib.check(L.kmpc_backtest_metrics(ctypes.byref(d), hist.data_ptr(), metrics.data_ptr(), sh))
-        return True
+        if _run_persistent(km, pp, strategy.mpc_config, entry, P, w, value, hist, metrics):
+            return True
+        if explicit:
+            raise ValueError("persistent=True: no persistent backtest kernel for this shape")
+        return False
 
     def run_steps():
         y = None
@@ -459,14 +484,8 @@ def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: Back
         raise ValueError(f"bt_cost_coeffs has {len(btc)} entries for {C} configs")
     km = strategy.device_model()
     dev = km.device
-    x = torch.as_tensor(obs).to(dev, torch.float32)
-    r = torch.as_tensor(realized).to(dev, torch.float32).contiguous()
-    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2]:
-        raise ValueError("obs must be [P, T, obs] and realized [P, T, N]")
-    P, T, N = r.shape
-    n_rows = T if n_rows is None else int(n_rows)
-    steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
-    S = len(steps)
+    pp = _prepare_paths(km, obs, realized, config, mean, std, n_rows)
+    x, r, P, N, S, n_rows = pp.x, pp.r, pp.P, pp.N, pp.S, pp.n_rows
     H = int(cfgs[0].horizon)
     kern = [j for j, c in enumerate(cfgs) if float(c.max_turnover) > 0 and math.isfinite(float(c.max_turnover))
             and math.isfinite(float(c.cost_coeff))]
@@ -478,44 +497,19 @@ def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: Back
     metrics = torch.empty((Ck * P, 5), dtype=torch.float64, device=dev)
 
     def run_kernel() -> bool:
-        """False (nothing run) where the C ABI has no sweep kernel for this shape."""
-        if _box_limit(cfgs[0], N):   # (equal across the configs, _sweep_configs) no box sweep kernel
-            return False
+        """Every step of every (config, path) in kmpc_backtest_sweep launches (_run_persistent): False
+        (nothing run) where there is no sweep kernel for this shape. (A position limit, max_weight, is
+        equal across the configs: _sweep_configs.)"""
         d = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
-        sdesc = _solve_desc(Ck * P, N, H, cfgs[0], False)
         f64 = dict(dtype=torch.float64, device=dev)
         pc = torch.tensor([float(cfgs[j].cost_coeff) for j in kern], **f64)
         pt = torch.tensor([float(cfgs[j].max_turnover) for j in kern], **f64)
         pb = torch.tensor([btc[j] for j in kern], **f64)
-        target = torch.empty((Ck * P, N), **f64)
-        status = torch.empty((Ck * P,), dtype=torch.int32, device=dev)
-        objv = torch.empty((Ck * P,), **f64)
-        sh = _lib.stream_handle(dev)
 
-        def call(k0, n, y, rr, n_real):
-            return L.kmpc_backtest_sweep(ctypes.byref(d), ctypes.byref(sdesc), Ck, pc.data_ptr(), pt.data_ptr(),
-                                         pb.data_ptr(), k0, n, y, rr, n_real, w.data_ptr(), value.data_ptr(),
-                                         hist.data_ptr(), target.data_ptr(), status.data_ptr(), objv.data_ptr(), sh)
+        def entry(sdesc, *a):
+            return L.kmpc_backtest_sweep(ctypes.byref(d), sdesc, Ck, pc.data_ptr(), pt.data_ptr(), pb.data_ptr(), *a)
 
-        rc = call(0, 0, None, None, 0)   # (shape check only)
-        if rc == _lib.KMPC_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        xt = x.transpose(0, 1).contiguous()
-        rt = r.transpose(0, 1).contiguous()
-        m, sd = km._stats(mean, std, N)
-        sc = max(1, PREROLL_CHUNK // P)          # steps per batched rollout
-        steps_t = torch.as_tensor(steps, dtype=torch.long, device=dev)
-        for k0 in range(0, S, sc):
-            n = min(sc, S - k0)
-            y = km.rollout(xt[steps_t[k0:k0 + n]].reshape(n * P, -1), m, sd, H, N).contiguous()
-            tn = steps_t[k0:k0 + n] + 1
-            n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
-            rr = rt[tn[:n_real]].contiguous() if n_real else None
-            _lib.check(call(k0, n, y.data_ptr(), rr.data_ptr() if rr is not None else None, n_real))
-        dm = _lib.BacktestDesc(Ck * P, N, max(S, 1), 0.0)
-        _lib.check(L.kmpc_backtest_metrics(ctypes.byref(dm), hist.data_ptr(), metrics.data_ptr(), sh))
-        return True
+        return _run_persistent(km, pp, cfgs[0], entry, Ck * P, w, value, hist, metrics)
 
     with torch.cuda.device(dev):
         if not (Ck and P and S and run_kernel()):

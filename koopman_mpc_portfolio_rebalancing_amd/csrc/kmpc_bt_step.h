@@ -1,7 +1,8 @@
 // kmpc_bt_step.h — one step of run_backtest's bookkeeping for one path (backtest.py:173-217),
 // shared by the lock-step kernel (kmpc_backtest.hip: bt_step_kernel, one launch per step) and the
-// path-persistent backtest kernel (kmpc_solve_c3.hip: after each step's solve in the same
-// workgroup). One code path, so the two are bit-identical.
+// path-persistent backtest kernel in its run and sweep forms (kmpc_bt_run.h, in every unit that
+// instantiates it: after each step's solve in the same workgroup or lane group). One code path, so
+// the two are bit-identical.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -33,7 +34,7 @@ struct StepArgs {
 };
 
 // path p's step a.k; red: >= blockDim / 64 doubles of LDS. Every thread of the block calls it.
-// pr: the row of a.realized the path reads (p itself, or in the sweep kernel, kmpc_bt_sweep.h, the
+// pr: the row of a.realized the path reads (p itself, or in the sweep form of kmpc_bt_run.h, the
 // environment path that the configs share).
 __device__ __forceinline__ void bt_step_body(const StepArgs& a, int p, int pr, double* red) {
     const double* tg = a.target + (size_t)p * a.N;

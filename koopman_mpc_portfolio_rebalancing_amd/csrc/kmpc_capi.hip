@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "kmpc_internal.h"
+#include "kmpc_solve_args.h"
 
 namespace {
 
@@ -20,6 +21,30 @@ int check_solve(const kmpc_solve_desc* d) {
     if (d->precision < KMPC_PRECISION_AUTO || d->precision > KMPC_PRECISION_MIXED) return KMPC_ERR_INVALID;
     if (!(d->mu_handoff < 1.0)) return KMPC_ERR_INVALID;   // (NaN too)
     return KMPC_OK;
+}
+
+// kmpc_backtest_run (the batch is the paths) and kmpc_backtest_sweep (the batch is configs x paths; the
+// configs carry c and tau, sdesc's are not read). l: the caller's arguments; P, S and cost come from desc.
+int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
+                   kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
+    if (!desc || !sdesc || desc->P < 0 || desc->N < 1 || desc->S < 1 || l.step0 < 0 || l.n_steps < 0 ||
+        l.step0 + l.n_steps > desc->S || l.n_real < 0 || l.n_real > l.n_steps || sdesc->N != desc->N)
+        return KMPC_ERR_INVALID;
+    if (sweep && (n_cfg < 1 || (long long)n_cfg * desc->P > 0x7fffffffLL)) return KMPC_ERR_INVALID;
+    kmpc_solve_desc sd = *sdesc;
+    sd.B = sweep ? n_cfg * desc->P : desc->P;
+    if (sweep) {
+        sd.cost_coeff = 0.0;
+        sd.max_turnover = 1.0;
+    }
+    const int rc = check_solve(&sd);
+    if (rc) return rc;
+    if (desc->P > 0 && l.n_steps > 0 &&
+        (!l.yhat || !l.weights || !l.value || !l.hist || !target || !status || !obj || (l.n_real > 0 && !l.realized) ||
+         (sweep && (!l.mpc_cost || !l.max_turnover || !l.bt_cost))))
+        return KMPC_ERR_INVALID;
+    l.P = desc->P; l.S = desc->S; l.cost = desc->cost_coeff;
+    return kmpc::backtest_launch(desc, &sd, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -141,41 +166,18 @@ int kmpc_backtest_step(const kmpc_backtest_desc* desc, int step, const double* t
 int kmpc_backtest_run(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int step0, int n_steps,
                       const float* yhat, const float* realized, int n_real, double* weights, double* value,
                       double* hist, double* target, int* status, double* obj, void* stream) {
-    if (!desc || !sdesc || desc->P < 0 || desc->N < 1 || desc->S < 1 || step0 < 0 || n_steps < 0 ||
-        step0 + n_steps > desc->S || n_real < 0 || n_real > n_steps || sdesc->N != desc->N)
-        return KMPC_ERR_INVALID;
-    kmpc_solve_desc sd = *sdesc;   // (the batch is the paths)
-    sd.B = desc->P;
-    const int rc = check_solve(&sd);
-    if (rc) return rc;
-    if (desc->P > 0 && n_steps > 0 &&
-        (!yhat || !weights || !value || !hist || !target || !status || !obj || (n_real > 0 && !realized)))
-        return KMPC_ERR_INVALID;
-    return kmpc::backtest_run_launch(desc, &sd, step0, n_steps, yhat, realized, n_real, weights, value, hist,
-                                     target, status, obj, (hipStream_t)stream);
+    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, nullptr, nullptr, nullptr,
+                              yhat, realized, weights, value, hist};
+    return backtest_entry(false, desc, sdesc, 0, l, target, status, obj, stream);
 }
 
 int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
                         const double* mpc_cost, const double* max_turnover, const double* bt_cost, int step0,
                         int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
                         double* value, double* hist, double* target, int* status, double* obj, void* stream) {
-    if (!desc || !sdesc || desc->P < 0 || desc->N < 1 || desc->S < 1 || step0 < 0 || n_steps < 0 ||
-        step0 + n_steps > desc->S || n_real < 0 || n_real > n_steps || sdesc->N != desc->N || n_cfg < 1 ||
-        (long long)n_cfg * desc->P > 0x7fffffffLL)
-        return KMPC_ERR_INVALID;
-    kmpc_solve_desc sd = *sdesc;   // (the batch is configs x paths; the configs carry c and tau)
-    sd.B = n_cfg * desc->P;
-    sd.cost_coeff = 0.0;
-    sd.max_turnover = 1.0;
-    const int rc = check_solve(&sd);
-    if (rc) return rc;
-    if (desc->P > 0 && n_steps > 0 &&
-        (!mpc_cost || !max_turnover || !bt_cost || !yhat || !weights || !value || !hist || !target || !status ||
-         !obj || (n_real > 0 && !realized)))
-        return KMPC_ERR_INVALID;
-    return kmpc::backtest_sweep_launch(desc, &sd, n_cfg, mpc_cost, max_turnover, bt_cost, step0, n_steps, yhat,
-                                       realized, n_real, weights, value, hist, target, status, obj,
-                                       (hipStream_t)stream);
+    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
+                              yhat, realized, weights, value, hist};
+    return backtest_entry(true, desc, sdesc, n_cfg, l, target, status, obj, stream);
 }
 
 int kmpc_standardize(int T, int N, const double* log_returns, const double* mean, const double* std,

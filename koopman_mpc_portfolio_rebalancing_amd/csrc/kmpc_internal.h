@@ -15,14 +15,11 @@ int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_pr
 int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
                      double* w_out, int* status, double* obj, int* iters, hipStream_t stream);
 
-int backtest_run_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int step0, int n_steps,
-                        const float* yhat, const float* realized, int n_real, double* weights, double* value,
-                        double* hist, double* target, int* status, double* obj, hipStream_t stream);
-
-int backtest_sweep_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const double* mpc_cost,
-                          const double* max_turnover, const double* bt_cost, int step0, int n_steps,
-                          const float* yhat, const float* realized, int n_real, double* weights, double* value,
-                          double* hist, double* target, int* status, double* obj, hipStream_t stream);
+// the path-persistent backtest: the run (n_cfg = 0) or the sweep of n_cfg configs (BtLaunch:
+// kmpc_solve_args.h)
+struct BtLaunch;
+int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const BtLaunch& l,
+                    double* target, int* status, double* obj, hipStream_t stream);
 
 // kmpc_backtest.hip
 int gross_returns_launch(size_t n, const float* yhat, float* R, hipStream_t stream);

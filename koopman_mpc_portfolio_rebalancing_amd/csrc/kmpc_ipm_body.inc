@@ -1,12 +1,12 @@
 // kmpc_ipm_body.inc — the body of one window's interior-point solve, textually included by
-// ipm_kernel (kmpc_solve_kernel.h), by the path-persistent backtest kernels (kmpc_bt_run.h,
-// kmpc_bt_sweep.h: once per step) and, once per phase, by the fused mixed-precision kernel
+// ipm_kernel (kmpc_solve_kernel.h), by the path-persistent backtest kernels (kmpc_bt_run.h:
+// its run and sweep forms, once per step) and, once per phase, by the fused mixed-precision kernel
 // (kmpc_solve_c3.hip). An include rather than a function: ipm_kernel's instruction stream stays exactly
 // what it was (a call boundary, even inlined, reshuffles this kernel's register allocation).
 // Names in scope at the include: HM, MAXT, EXACT, FL, CS, QL, GL, PH, BOX (template parameters; BOX
 // a constant false where the kernel has no box form), Real,
 // NWM, args (SolveArgs), sh (Shared<HM, NWM, Real>&), b (the window: w_prev, outputs, warm record),
-// yb (the window's forecast in args.yhat: b, except where windows share forecasts, kmpc_bt_sweep.h),
+// yb (the window's forecast in args.yhat: b, except where windows share forecasts: the sweep, kmpc_bt_run.h),
 // hand (Handoff<HM, ON>: the iterate the phases of the fused kernel pass on in registers; the empty
 // form elsewhere, where PH = 1 / 2 / 3 go through the window's record in args.warm).
     // the iterate goes from phase to phase on chip (the fused kernel) or through args.warm

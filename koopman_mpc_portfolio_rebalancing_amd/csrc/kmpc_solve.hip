@@ -98,7 +98,7 @@ enum class Family { SIMPLEX, LARGE, PACKED, MIXED_C3, CASE, GENERIC };
 struct Plan {
     Family family;
     // PACKED, CASE: the rung is the C3 one, and the path-persistent backtest kernels have a form of
-    // it (float64, case 7, H = HM: launch_bt_*_variant; one step's W0 only)
+    // it (float64, case 7, H = HM: launch_bt_variant; one step's W0 only)
     bool c3 = false, persistent = false;
 };
 
@@ -247,60 +247,35 @@ int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* y
     });
 }
 
-// kmpc_backtest_run: a path-persistent kernel exists where kmpc_solve sends the per-step batch of P
-// windows to a float64 constant-case register kernel of case 7 (no short, cost and cap): H = 10 or
-// 5 with 32 < N <= 256, one window per workgroup, and the packed N <= 32 kernels with H = 2, 5 or
-// 10, one path per lane group — not the mixed pair. The persistent kernel runs that kernel's window
-// body, so the steps match it.
-int backtest_run_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int step0, int n_steps,
-                        const float* yhat, const float* realized, int n_real, double* weights, double* value,
-                        double* hist, double* target, int* status, double* obj, hipStream_t stream) {
-    kmpc_solve_desc d = *sd;
-    d.B = bd->P;
-    SolveArgs a = make_args(&d);
-    const Plan p = solve_plan(a, d.precision);   // (the kernel kmpc_solve picks for this batch of P windows)
+// kmpc_backtest_run (n_cfg = 0) and kmpc_backtest_sweep (n_cfg >= 1 configs over the same bd->P
+// paths), one launch of the path-persistent kernel (kmpc_bt_run.h) in its run or sweep form. The
+// kernel exists where kmpc_solve sends the batch of sd->B windows (the caller has set it: P for the
+// run, n_cfg P for the sweep) to a float64 constant-case register kernel of case 7 (no short, cost
+// and cap): H = 10 or 5 with 32 < N <= 256, one window per workgroup, and the packed N <= 32 kernels
+// with H = 2, 5 or 10, one work item per lane group — not the mixed pair. It runs that kernel's
+// window body, so the steps match it. The run plans with the caller's precision, cost_coeff and
+// max_turnover. The sweep's parameters are device arrays, so the constraint case cannot depend on
+// them: always the constant case 7 (the caller has set sd's cost_coeff and max_turnover to it) in
+// float64 — no mixed pair at any batch size, and none to ask for.
+int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const BtLaunch& l,
+                    double* target, int* status, double* obj, hipStream_t stream) {
+    const bool sweep = n_cfg > 0;
+    SolveArgs a = make_args(sd);
+    if (sweep && sd->precision == KMPC_PRECISION_MIXED) return KMPC_ERR_UNSUPPORTED;
+    // (the kernel kmpc_solve picks for this batch)
+    const Plan p = solve_plan(a, sweep ? KMPC_PRECISION_F64 : sd->precision);
     if (!p.persistent) return KMPC_ERR_UNSUPPORTED;
-    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
+    if (bd->P == 0 || l.n_steps == 0) return KMPC_OK;
     a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
-    a.yhat = yhat; a.wp = weights;
-    const auto run = [&](auto launch) {
-        return launch(a, n_steps, n_real, yhat, realized, step0, bd->S, bd->cost_coeff, weights, value, hist, stream);
+    a.yhat = l.yhat; a.wp = l.weights;
+    const auto run = [&](auto sw) {
+        constexpr bool SW = decltype(sw)::value;
+        if (p.family == Family::PACKED)
+            return by_horizon(a.H, [&](auto hm) { return launch_bt_packed<decltype(hm)::value, SW>(a, l, stream); });
+        if (p.c3) return launch_bt_c3<SW>(a, l, stream);
+        return a.H == 5 ? launch_bt_case<5, SW>(a, l, stream) : launch_bt_case<10, SW>(a, l, stream);
     };
-    if (p.family == Family::PACKED)
-        return by_horizon(a.H, [&](auto hm) { return run(launch_bt_run_packed<decltype(hm)::value>); });
-    if (p.c3) return run(launch_bt_run_c3);
-    return a.H == 5 ? run(launch_bt_run_case<5>) : run(launch_bt_run_case<10>);
-}
-
-// kmpc_backtest_sweep: n_cfg configs over the same bd->P paths in one launch of the sweep form of
-// the path-persistent kernel (kmpc_bt_sweep.h), for the shapes backtest_run_launch covers. The
-// configs' parameters are device arrays, so the constraint case cannot depend on them: always the
-// constant case 7 in float64 (no mixed pair at any batch size), packed as pack_small says for a
-// batch of n_cfg P windows. sd's cost_coeff, max_turnover and B are not read.
-int backtest_sweep_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const double* mpc_cost,
-                          const double* max_turnover, const double* bt_cost, int step0, int n_steps,
-                          const float* yhat, const float* realized, int n_real, double* weights, double* value,
-                          double* hist, double* target, int* status, double* obj, hipStream_t stream) {
-    kmpc_solve_desc d = *sd;
-    d.B = n_cfg * bd->P;
-    d.cost_coeff = 0.0;
-    d.max_turnover = 1.0;   // (case 7; the kernel reads the configs' own)
-    SolveArgs a = make_args(&d);
-    if (d.precision == KMPC_PRECISION_MIXED) return KMPC_ERR_UNSUPPORTED;
-    const Plan p = solve_plan(a, KMPC_PRECISION_F64);
-    if (!p.persistent) return KMPC_ERR_UNSUPPORTED;
-    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
-    a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
-    a.yhat = yhat; a.wp = weights;
-    SweepLaunch l;
-    l.P = bd->P; l.n_steps = n_steps; l.n_real = n_real; l.step0 = step0; l.S = bd->S;
-    l.mpc_cost = mpc_cost; l.max_turnover = max_turnover; l.bt_cost = bt_cost;
-    l.yhat = yhat; l.realized = realized;
-    l.weights = weights; l.value = value; l.hist = hist;
-    if (p.family == Family::PACKED)
-        return by_horizon(a.H, [&](auto hm) { return launch_bt_sweep_packed<decltype(hm)::value>(a, l, stream); });
-    if (p.c3) return launch_bt_sweep_c3(a, l, stream);
-    return a.H == 5 ? launch_bt_sweep_case<5>(a, l, stream) : launch_bt_sweep_case<10>(a, l, stream);
+    return sweep ? run(std::true_type{}) : run(std::false_type{});
 }
 
 }  // namespace kmpc

@@ -50,9 +50,9 @@ size_t mixed_warm_floats(int H, int N);
 
 // ---- The variant ladder: which ipm_kernel<HM, MAXT, EXACT, FL, CS, QL, GL> a shape gets. ----
 // Written once and visited by kmpc_solve (launch_ipm_packed / launch_ipm_case), by the
-// path-persistent backtest (kmpc_bt_run.h) and by its sweep form (kmpc_bt_sweep.h), each with its own
-// launch as the callable, and by the host plan (kmpc_solve.hip) with a probe: the backtest kernels
-// run the window body of exactly the variant kmpc_solve picks for the same batch.
+// path-persistent backtest in its run and sweep forms (kmpc_bt_run.h), each with its own launch as
+// the callable, and by the host plan (kmpc_solve.hip) with a probe: the backtest kernels run the
+// window body of exactly the variant kmpc_solve picks for the same batch.
 constexpr int WAVE = 64;
 constexpr int QL_CS = 104;      // cold-array stride of the 128-thread QL variant (N < QL_CS assets)
 constexpr int QL_CS256 = 216;   // ... and of the 256-thread one
@@ -143,34 +143,27 @@ int launch_ipm_case(const SolveArgs& a, hipStream_t stream);
 // the C3 kernel (H = 10, FL = 7, 128 threads, LDL^T arrays in LDS) in its own -O2 unit
 // (kmpc_solve_c3.hip): float64, or with a.warm set the mixed-precision pair
 int launch_ipm_c3(const SolveArgs& a, hipStream_t stream);
-// the path-persistent backtest kernel of the C3 shape (kmpc_solve_c3.hip): a.B = paths, a.wout the
-// [P, N] W0 scratch, a.status / a.obj [P] scratch; n_steps steps from history row step0
-int launch_bt_run_c3(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
-                     int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream);
-// ... and of the constant-case shapes H = HM (kmpc_solve_hbt*.hip); KMPC_ERR_UNSUPPORTED elsewhere
-template <int HM>
-int launch_bt_run_case(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
-                       int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream);
-// ... and of the packed shapes (N <= 32, H = HM, one lane group per path; kmpc_solve_p*.hip)
-template <int HM>
-int launch_bt_run_packed(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
-                         int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream);
-// The sweep form of the path-persistent kernel (kmpc_bt_sweep.h, kmpc_backtest_sweep): a.B = C P
-// work items (config-major), a.wout the [C P, N] W0 scratch, a.status / a.obj [C P] scratch; a.c and
-// a.tau are not read (the kernel takes them per config from the device arrays). Always case 7.
-struct SweepLaunch {
-    int P, n_steps, n_real, step0, S;
+// One launch of the path-persistent backtest kernel (kmpc_bt_run.h) in its two forms. The run
+// (kmpc_backtest_run): a.B = P paths, a.wout the [P, N] W0 scratch, a.status / a.obj [P] scratch,
+// cost the bookkeeping's cost_coeff, the three per-config arrays null. The sweep
+// (kmpc_backtest_sweep): a.B = C P work items (config-major), the scratch sized for them; a.c, a.tau
+// and cost are not read (the kernel takes them per config from the device arrays). Always case 7.
+struct BtLaunch {
+    int P, n_steps, n_real, step0, S;                  // n_steps steps from history row step0 of S
+    double cost;
     const double *mpc_cost, *max_turnover, *bt_cost;   // [C] device
     const float *yhat, *realized;                      // [n_steps, P, H, N], [n_steps, P, N]
     double *weights, *value, *hist;                    // [C P, N], [C P], [C P, S, 4]
 };
-// ... of the C3 shape (kmpc_solve_c3sw.hip), the constant-case shapes H = HM (kmpc_solve_hsw*.hip)
-// and the packed shapes (kmpc_solve_psw*.hip); KMPC_ERR_UNSUPPORTED elsewhere
-int launch_bt_sweep_c3(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
-template <int HM>
-int launch_bt_sweep_case(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
-template <int HM>
-int launch_bt_sweep_packed(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream);
+// ... of the C3 shape (the run: kmpc_solve_c3.hip, the sweep: kmpc_solve_c3sw.hip), the constant-case
+// shapes H = HM (kmpc_solve_hbt*.hip, kmpc_solve_hsw*.hip) and the packed shapes (N <= 32, H = HM, one
+// lane group per work item; kmpc_solve_p*.hip, kmpc_solve_psw*.hip); KMPC_ERR_UNSUPPORTED elsewhere
+template <bool SWEEP>
+int launch_bt_c3(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
+template <int HM, bool SWEEP>
+int launch_bt_case(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
+template <int HM, bool SWEEP>
+int launch_bt_packed(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 // packed small-window kernels, 64 / GL windows per wave (kmpc_solve_p*.hip); KMPC_ERR_UNSUPPORTED
 // outside N <= 32, 3 H <= 32
 template <int HM>

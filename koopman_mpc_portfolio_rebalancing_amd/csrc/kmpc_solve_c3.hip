@@ -98,11 +98,7 @@ int launch_ipm_c3(const SolveArgs& a, hipStream_t stream) {
     return launch_one<10, 128, true, 7, QL_CS, true>(a, stream);
 }
 
-int launch_bt_run_c3(const SolveArgs& a, int n_steps, int n_real, const float* yhat, const float* realized,
-                     int step0, int S, double c, double* weights, double* value, double* hist, hipStream_t stream) {
-    return launch_bt_run_one<10, 128, true, 7, QL_CS, true>(a, n_steps, n_real, yhat, realized, step0, S, c, weights,
-                                                           value, hist, stream);
-}
+template int launch_bt_c3<false>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 }  // namespace kmpc
 
 #ifdef KMPC_STATS

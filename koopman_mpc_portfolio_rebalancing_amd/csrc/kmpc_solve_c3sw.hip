@@ -1,4 +1,4 @@
-// kmpc_solve_c3sw.hip — the sweep form of the path-persistent backtest kernel (kmpc_bt_sweep.h) of
+// kmpc_solve_c3sw.hip — the sweep form of the path-persistent backtest kernel (kmpc_bt_run.h) of
 // the C3 shape (H = 10, N < 104: 128 threads, the LDL^T arrays in LDS), built with the options of
 // kmpc_solve_c3.hip, whose kernel it mirrors.
 #ifndef KMPC_SCHUR_BCAST_F64   // as kmpc_solve_c3.hip
@@ -8,10 +8,8 @@
 #define KMPC_FD_WAIT_ONCE_F64 0   // form moved the sibling backtest kernel's allocation and ran behind
 #endif
 #include "kmpc_solve_kernel.h"
-#include "kmpc_bt_sweep.h"
+#include "kmpc_bt_run.h"
 
 namespace kmpc {
-int launch_bt_sweep_c3(const SolveArgs& a, const SweepLaunch& l, hipStream_t stream) {
-    return launch_bt_sweep_one<10, 128, true, 7, QL_CS, true>(a, l, stream);
-}
+template int launch_bt_c3<true>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 }  // namespace kmpc

@@ -3,7 +3,5 @@
 #include "kmpc_bt_run.h"
 
 namespace kmpc {
-template int launch_bt_run_case<5>(const SolveArgs& a, int n_steps, int n_real, const float* yhat,
-                                    const float* realized, int step0, int S, double c, double* weights,
-                                    double* value, double* hist, hipStream_t stream);
+template int launch_bt_case<5, false>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 }  // namespace kmpc

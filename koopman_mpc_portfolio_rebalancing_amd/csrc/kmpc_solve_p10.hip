@@ -6,7 +6,5 @@
 namespace kmpc {
 template int launch_ipm_packed<10>(const SolveArgs& a, hipStream_t stream);
 // the path-persistent backtest kernels of the packed shapes (kmpc_bt_run.h)
-template int launch_bt_run_packed<10>(const SolveArgs& a, int n_steps, int n_real, const float* yhat,
-                                      const float* realized, int step0, int S, double c, double* weights,
-                                      double* value, double* hist, hipStream_t stream);
+template int launch_bt_packed<10, false>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 }  // namespace kmpc

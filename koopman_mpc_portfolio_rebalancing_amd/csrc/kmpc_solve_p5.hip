@@ -8,10 +8,6 @@ template int launch_ipm_packed<2>(const SolveArgs& a, hipStream_t stream);
 template int launch_ipm_packed<5>(const SolveArgs& a, hipStream_t stream);
 // the path-persistent backtest kernels of the packed shapes (kmpc_bt_run.h), built with this unit's
 // options like the kernels they mirror
-template int launch_bt_run_packed<2>(const SolveArgs& a, int n_steps, int n_real, const float* yhat,
-                                     const float* realized, int step0, int S, double c, double* weights,
-                                     double* value, double* hist, hipStream_t stream);
-template int launch_bt_run_packed<5>(const SolveArgs& a, int n_steps, int n_real, const float* yhat,
-                                     const float* realized, int step0, int S, double c, double* weights,
-                                     double* value, double* hist, hipStream_t stream);
+template int launch_bt_packed<2, false>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
+template int launch_bt_packed<5, false>(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 }  // namespace kmpc

@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
 """Compare two directories of device-only assembly (csrc/Makefile: `make asm`) kernel by kernel.
 
-    python tools/asm_compare.py BEFORE_DIR AFTER_DIR [--moved KERNEL_SUBSTRING=UNIT ...] > report.md
+    python tools/asm_compare.py BEFORE_DIR AFTER_DIR [--moved KERNEL_SUBSTRING=UNIT ...]
+                                [--renamed OLD=NEW ...] > report.md
 
 For every unit (<unit>.s in either directory) and every kernel in it the script compares
   - the body: the lines between the kernel's symbol label and its `.Lfunc_end<k>` label, with
-    comments stripped and the function's index k within the unit normalised away in local labels
-    (`.LBB<k>_12`, `.Lfunc_end<k>`, `.Ltmp...` are positional: kernels that leave a unit renumber them);
+    comments stripped, the kernel's own symbol and the function's index k within the unit normalised
+    away (local labels `.LBB<k>_12`, `.Lfunc_end<k>`, `.Ltmp...` are positional: kernels that leave a
+    unit renumber them);
   - the metadata: VGPR / AGPR / SGPR counts, spill counts, private segment (scratch) and LDS size.
 A kernel that moved to another unit (--moved simplex_kernel=kmpc_solve_simplex) is compared across
-the two units. Prints a markdown report; exit status 1 if any kernel present on both sides differs.
+the two units. A kernel that was renamed (--renamed bt_run_kernel=bt_kernel) is paired with the
+kernel whose demangled name is the same after the substitution — same parameter list, same template
+arguments or those plus an added trailing pack — and both names are reported. Prints a markdown
+report; exit status 1 if any kernel present on both sides differs.
 """
 import argparse
+import functools
 import os
 import re
 import sys
@@ -38,7 +44,7 @@ def parse_unit(path):
                 ln = re.sub(r"\.LBB\d+_", ".LBB_", ln)
                 ln = re.sub(r"\.L(func_end|func_begin|tmp)\d+", r".L\1", ln)
                 if ln.strip():
-                    body.append(ln)
+                    body.append(ln.replace(name, "<self>"))
                 i += 1
             bodies[name] = body
         i += 1
@@ -66,6 +72,7 @@ def _close(block, meta):
         meta[d[".name"]] = {k: d.get(k, "-") for k in META_KEYS}
 
 
+@functools.lru_cache(maxsize=None)
 def short(name):
     try:
         import subprocess
@@ -75,14 +82,37 @@ def short(name):
         return name
 
 
+def split_name(dem):
+    """demangled `void f<targs>(params)` -> (`void f`, targs, params)"""
+    m = re.match(r"([^<(]*)(?:<(.*)>)?\((.*)\)$", dem)
+    return m.groups(default="") if m else (dem, "", "")
+
+
+def renamed_to(k, renamed, candidates):
+    """The symbol among candidates that kernel k is called after --renamed, or None"""
+    for old, new in renamed.items():
+        if old not in short(k):
+            continue
+        name, targs, params = split_name(short(k))
+        name = name.replace(old, new)
+        for k2 in candidates:
+            n2, t2, p2 = split_name(short(k2))
+            if n2 == name and p2 == params and (t2 == targs or t2.startswith(targs + ", ")):
+                return k2
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("--moved", action="append", default=[], metavar="SUBSTR=UNIT",
                     help="kernels whose symbol contains SUBSTR are looked up in UNIT on the after side")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW",
+                    help="kernels whose name contains OLD are paired with the one named with NEW in its place")
     a = ap.parse_args()
     moved = dict(m.split("=", 1) for m in a.moved)
+    renamed = dict(m.split("=", 1) for m in a.renamed)
     units = sorted({f[:-2] for d in (a.before, a.after) for f in os.listdir(d) if f.endswith(".s")})
     parsed = {side: {u: parse_unit(os.path.join(d, u + ".s")) if os.path.exists(os.path.join(d, u + ".s")) else {}
                      for u in units} for side, d in (("b", a.before), ("a", a.after))}
@@ -94,18 +124,21 @@ def main():
     for u in units:
         for k, (body, meta) in parsed["b"][u].items():
             u2 = next((dst for sub, dst in moved.items() if sub in k), u)
-            other = parsed["a"].get(u2, {}).get(k)
-            if other is None:
+            after = parsed["a"].get(u2, {})
+            k2 = k if k in after else renamed_to(k, renamed, after)
+            if k2 is None:
                 gone.append((u, k))
                 continue
-            claimed.add((u2, k))
+            other = after[k2]
+            claimed.add((u2, k2))
             same = body == other[0] and meta == other[1] and len(body) > 0
             n_same += same
             n_diff += not same
             where = u if u2 == u else f"{u} -> {u2}"
             verdict = "identical" if same else "**DIFFERS** (after: %d lines, %s)" % (len(other[0]), other[1])
             print("| %s | `%s` | %d | %s / %s / %s | %s / %s | %s | %s | %s |" % (
-                where, short(k), len(body), meta[".vgpr_count"], meta[".agpr_count"], meta[".sgpr_count"],
+                where, short(k) if k2 == k else "%s` -> `%s" % (short(k), short(k2)), len(body),
+                meta[".vgpr_count"], meta[".agpr_count"], meta[".sgpr_count"],
                 meta[".vgpr_spill_count"], meta[".sgpr_spill_count"], meta[".private_segment_fixed_size"],
                 meta[".group_segment_fixed_size"], verdict))
     for u in units:
