@@ -399,6 +399,62 @@ int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int 
                          const float* mean, const float* std, const int* ts,
                          double* mu, double* sigma, int* valid, void* stream);
 
+/* The moments of kmpc_rolling_moments for n_ts test rows of P panels in one launch (added within
+ * ABI 0.7.0): z [P, T, ldz] holds P standardized panels of T rows each, and window (s, p) is the one
+ * kmpc_rolling_moments computes at test row ts[s] of panel p — its rows stay inside that panel.
+ * Outputs are step-major: mu [n_ts, P, N], sigma [n_ts, P, N, N], valid [n_ts, P] (the layout
+ * kmpc_markowitz_run reads). Same kernel arithmetic: with P = 1 the results equal
+ * kmpc_rolling_moments(B = n_ts) bit for bit. P * n_ts must fit an int. */
+int kmpc_rolling_moments_paths(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                               const float* mean, const float* std, const int* ts,
+                               double* mu, double* sigma, int* valid, void* stream);
+
+/* ---- Markowitz backtest: run_backtest(MarkowitzStrategy(...)) for P paths in ONE launch -------- */
+/* (added within ABI 0.7.0) Steps step0 .. step0 + n_steps - 1 of every path, each the strategy's
+ * window — kmpc_solve_mv_ws (kmpc_solve_mv_box under a limit) of that step's moments from the path's
+ * current weights where valid, else the hold (target = current weights, baselines.py:76-78) — then
+ * the kmpc_backtest_step bookkeeping, run back to back by one workgroup per path, as
+ * kmpc_backtest_run does for the log-utility solve. The results are bit-identical to the per-step
+ * loop of those calls: the same window solve and the same bookkeeping sums.
+ *   bdesc:      P paths, N assets, S history rows, cost_coeff (as kmpc_backtest_run).
+ *   mvdesc:     the solve's program; B is ignored (the batch is bdesc->P), N must equal bdesc->N,
+ *               return_full_W must be 0 (KMPC_ERR_INVALID otherwise).
+ *   max_weight: 0: no position limit. Otherwise the rules of kmpc_solve_mv_box in its order: NaN or
+ *               < 0 KMPC_ERR_INVALID; allow_short KMPC_ERR_UNSUPPORTED; >= 1 an inactive bound (the
+ *               plain kernels); N * max_weight <= 1 KMPC_ERR_INVALID.
+ *   mu [n_steps, P, H, N] f64, sigma [n_steps, P, N, N] f64, valid [n_steps, P] int: the steps'
+ *               moments (kmpc_rolling_moments_paths for H = 1).
+ *   realized [n_steps, P, N] f32, n_real, weights [P,N], value [P], hist [P,S,4]: as kmpc_backtest_run.
+ *   target [P,N] f64, status [P] int, obj [P] f64: scratch (on return the last step's W0, status,
+ *               objective; a held step reports optimal and NaN).
+ *   workspace:  kmpc_mv_workspace_bytes of mvdesc with B = P (0 up to H*N = 128).
+ * Return codes, all decided before any launch: the argument rules above; KMPC_ERR_UNSUPPORTED past
+ * H*N = KMPC_MV_MAX_HN or H > KMPC_MV_MAX_H; then n_steps = 0 (the shape probe) or P = 0 return
+ * KMPC_OK; null arrays KMPC_ERR_INVALID; KMPC_ERR_WORKSPACE as kmpc_solve_mv_ws. */
+int kmpc_markowitz_run(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                       int step0, int n_steps, const double* mu, const double* sigma, const int* valid,
+                       const float* realized, int n_real, double* weights, double* value, double* hist,
+                       double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                       void* stream);
+
+/* A sweep of kmpc_markowitz_run over the baseline's hyper-parameters in ONE launch (added within
+ * ABI 0.7.0): n_cfg configs — a risk aversion gamma[j], the solve's cost_coeff mv_cost[j] and the
+ * bookkeeping's cost_coeff bt_cost[j], float64 DEVICE arrays — over the same bdesc->P paths, one
+ * workgroup per (config j, path p). Rows are config-major, as kmpc_backtest_sweep: row j * P + p of
+ * weights / value / hist / target / status / obj; the moments and the realized returns depend on the
+ * path only and are shared by the configs. mvdesc's gamma and cost_coeff and bdesc's cost_coeff are
+ * ignored; there is one max_weight (and one allow_short) per launch. A config with gamma[j] < 0,
+ * mv_cost[j] < 0 or a non-finite one ends every step KMPC_STATUS_SOLVER_ERROR with the hold
+ * fallback (turnover and cost 0); the other configs are not affected. n_cfg < 1 (or n_cfg * P past
+ * an int) is KMPC_ERR_INVALID; every other rule as kmpc_markowitz_run, the workspace that of mvdesc
+ * with B = n_cfg * P. Config j's rows are bit-identical to kmpc_markowitz_run with its parameters. */
+int kmpc_markowitz_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                         int n_cfg, const double* gamma, const double* mv_cost, const double* bt_cost,
+                         int step0, int n_steps, const double* mu, const double* sigma, const int* valid,
+                         const float* realized, int n_real, double* weights, double* value, double* hist,
+                         double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                         void* stream);
+
 /* Workspace needed by kmpc_rollout / kmpc_solve / kmpc_window (either desc may be NULL; with both,
    the sum for kmpc_window: rollout scratch + yhat + the solve's). */
 size_t kmpc_workspace_bytes(const kmpc_rollout_desc* rdesc, const kmpc_solve_desc* sdesc);
@@ -417,7 +473,9 @@ const char* kmpc_strerror(int code);
    only — no struct, enum or existing function changed, so every caller built against 0.7.0 keeps
    working unchanged and the version string did not move; a caller that needs the function checks
    for the symbol (dlsym) rather than for a version. kmpc_solve_mv_box was added within 0.7.0 in the
-   same way: a new function only, kmpc_mv_desc and every existing function unchanged. */
+   same way: a new function only, kmpc_mv_desc and every existing function unchanged.
+   kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep were added within 0.7.0 in
+   the same way: three new functions, no struct, enum or existing function changed. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

@@ -11,5 +11,6 @@ from .koopman import DeviceKoopman, KoopmanModelSpec, standardize_panel  # noqa:
 from .backtest import (BacktestConfig, BuyAndHoldStrategy, KoopmanMPCStrategy, Strategy,  # noqa: F401
                        calculate_metrics, run_backtest, run_backtest_lockstep, run_backtest_sweep,
                        sweep_backtest)
+from .baselines import run_markowitz_lockstep, run_markowitz_sweep, sweep_backtest_markowitz  # noqa: F401
 
 __version__ = "0.7.0"

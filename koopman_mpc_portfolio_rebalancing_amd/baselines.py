@@ -11,19 +11,25 @@ encoder / decoder and the latent operator A^T (row-vector convention, z <- z @ A
 Mirrors ``MarkowitzStrategy`` (baselines.py:24-106): the rolling 60-row mean / covariance of the
 de-standardized current returns (kmpc_rolling_moments) and the H = 1 mean-variance solve
 (kmpc_solve_mv, mpc.py:119-184; kmpc_solve_mv_box under a per-asset position limit) run on the
-device, for one window (``rebalance``) or many (``rebalance_batch``).
+device, for one window (``rebalance``) or many (``rebalance_batch``). A whole Markowitz backtest of P
+paths runs on the device too (``run_markowitz_lockstep``: every step of a path in one
+kmpc_markowitz_run launch), as does a sweep of the baseline's two hyper-parameters over shared
+moments (``run_markowitz_sweep`` / ``sweep_backtest_markowitz``: kmpc_markowitz_sweep).
 """
 from __future__ import annotations
 
-from typing import Any, Sequence
+import ctypes
+from typing import Any, Dict, Optional, Sequence
 
 import numpy as np
+import pandas as pd
 import torch
 
 from . import _lib
-from .backtest import KoopmanMPCStrategy, Strategy, _cache_hit, _cache_key, _env_stats
+from .backtest import (METRIC_NAMES, BacktestConfig, KoopmanMPCStrategy, Strategy, _cache_hit, _cache_key,
+                       _env_stats, run_backtest)
 from .koopman import KoopmanModelSpec
-from .mpc import MPCConfig, solve_mpc_mean_variance_batched
+from .mpc import MPCConfig, _box_limit, _mv_desc, _workspace, solve_mpc_mean_variance_batched
 
 
 def fit_dmd(train_data) -> np.ndarray:
@@ -181,5 +187,245 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         return W0[0]
 
 
+# ---- the Markowitz backtest on the device ------------------------------------------------------
+
+# Steps per chunk of run_markowitz_lockstep / run_markowitz_sweep: each chunk is one
+# kmpc_rolling_moments_paths and one kmpc_markowitz_run (or _sweep), and holds the chunk's Sigma,
+# chunk * P * N^2 * 8 bytes. At most MARKOWITZ_CHUNK steps, and fewer where that buffer would pass
+# MARKOWITZ_SIGMA_BYTES (256 MiB: P = 64 paths of N = 100 assets run 52 steps per chunk).
+MARKOWITZ_CHUNK = 1024
+MARKOWITZ_SIGMA_BYTES = 256 << 20
+
+
+def _markowitz_chunk(P: int, N: int) -> int:
+    return max(1, min(int(MARKOWITZ_CHUNK), int(MARKOWITZ_SIGMA_BYTES) // max(1, P * N * N * 8)))
+
+
+def _markowitz_paths(strategy, obs, realized, config: BacktestConfig, mean, std, n_rows: Optional[int]):
+    """The P paths of a Markowitz device backtest: the shape checks (ValueError before any device
+    work), then z [P, T, ld] and the realized rows [T, P, N] on the device, the steps' test indices,
+    the float32 de-standardisation and the solve's descriptor fields."""
+    from types import SimpleNamespace
+    x, r = torch.as_tensor(obs), torch.as_tensor(realized)
+    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2] or x.shape[2] < r.shape[2]:
+        raise ValueError("obs must be [P, T, >= N] and realized [P, T, N]")
+    P, T, N = (int(v) for v in r.shape)
+    H = int(strategy.mpc_config.horizon)
+    u = _box_limit(strategy.mpc_config, N)
+    n_rows = T if n_rows is None else int(n_rows)
+    steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
+    dev = strategy._device()
+    z = x.to(dev, torch.float32).contiguous()
+    rt = r.to(dev, torch.float32).transpose(0, 1).contiguous()
+    m = torch.as_tensor(np.asarray(mean, np.float64).astype(np.float32), device=dev)
+    sd = torch.as_tensor(np.asarray(std, np.float64).astype(np.float32), device=dev)
+    if m.numel() != N or sd.numel() != N:
+        raise ValueError(f"mean and std must have {N} entries")
+    return SimpleNamespace(z=z, rt=rt, P=P, T=T, N=N, H=H, u=u, steps=steps, S=len(steps), dev=dev, m=m, sd=sd,
+                           ts=torch.as_tensor(steps, dtype=torch.int32, device=dev))
+
+
+def _markowitz_chunks(pp, lookback: int):
+    """Per chunk of steps: (k0, n, mu [n, P, H, N], sigma [n, P, N, N], valid [n, P], the realized rows
+    [n_real, P, N] of the steps' t + 1 or None, n_real). One kmpc_rolling_moments_paths per chunk; a
+    horizon above 1 repeats the rolling mean in every period (the reference's strategy has H = 1)."""
+    L = _lib.load()
+    P, T, N, H, dev = pp.P, pp.T, pp.N, pp.H, pp.dev
+    sc = _markowitz_chunk(P, N)
+    for k0 in range(0, pp.S, sc):
+        n = min(sc, pp.S - k0)
+        mu = torch.empty((n, P, N), dtype=torch.float64, device=dev)
+        sigma = torch.empty((n, P, N, N), dtype=torch.float64, device=dev)
+        valid = torch.empty((n, P), dtype=torch.int32, device=dev)
+        ts = pp.ts[k0:k0 + n]
+        _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback), pp.z.data_ptr(), int(pp.z.shape[2]),
+                                                pp.m.data_ptr(), pp.sd.data_ptr(), ts.data_ptr(), mu.data_ptr(),
+                                                sigma.data_ptr(), valid.data_ptr(), _lib.stream_handle(dev)))
+        mu = mu[:, :, None, :].expand(n, P, H, N).contiguous()
+        tn = [t + 1 for t in pp.steps[k0:k0 + n] if t + 1 < T]   # (steps increase: a prefix has a t + 1)
+        rr = pp.rt[torch.as_tensor(tn, dtype=torch.long, device=dev)].contiguous() if tn else None
+        yield k0, n, mu, sigma, valid, rr, len(tn)
+
+
+def _markowitz_out(hist, w, metrics, S: int, lead: tuple) -> Dict[str, Any]:
+    hist = hist[..., :S, :]
+    out = {k: hist[..., i] for i, k in enumerate(("portfolio_value", "return", "turnover", "cost"))}
+    out["weights"] = w
+    metrics = metrics.reshape(*lead, 5)
+    out["metrics"] = {name: metrics[..., i] for i, name in enumerate(METRIC_NAMES)} if S else {}
+    return out
+
+
+def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config: BacktestConfig, mean, std,
+                           n_rows: Optional[int] = None, lookback_window: int = 60,
+                           persistent: Optional[bool] = None) -> Dict[str, Any]:
+    """P independent Markowitz backtests of the reference loop (backtest.py:133-219 with
+    MarkowitzStrategy.rebalance, baselines.py:48-106) on the device: path p reproduces
+    run_backtest(strategy, env, config) on an env whose test rows are obs[p] and whose de-standardized
+    realized log-returns are realized[p]. Arguments and the returned dict as run_backtest_lockstep.
+
+    Args:
+        strategy: a MarkowitzStrategy (risk_aversion, cost_coeff, allow_short, max_weight; the
+            horizon of its mpc_config, 1 in the reference).
+        obs: [P, T, >= N] float32 standardized test rows; the first N columns are the current returns.
+        realized: [P, T, N] float32 de-standardized log-returns (the reference's all_returns).
+        mean, std: [N] de-standardisation of the moments (env.stats).
+        n_rows: len(env.test_dataset) (default T); steps range(0, n_rows - config.horizon,
+            config.rebalance_freq), step t realizing row t + 1.
+        persistent: every step of a path in one launch per chunk of steps (kmpc_markowitz_run: the
+            step's solve or hold, then its bookkeeping, back to back in one workgroup per path).
+            False: the per-step loop — kmpc_solve_mv_ws / kmpc_solve_mv_box over the P windows, the
+            hold select, kmpc_backtest_step. Default: the persistent kernel wherever the C ABI has it
+            (H * N <= 1,024). The two are bit-identical.
+    The steps go in chunks of _markowitz_chunk(P, N), one kmpc_rolling_moments_paths each.
+    Returns: dict of device tensors — portfolio_value / return / turnover / cost [P, S], weights
+        [P, N] (after the last step), metrics {name: [P]}.
+    """
+    pp = _markowitz_paths(strategy, obs, realized, config, mean, std, n_rows)
+    P, N, H, S, dev = pp.P, pp.N, pp.H, pp.S, pp.dev
+    f64 = dict(dtype=torch.float64, device=dev)
+    w = torch.full((P, N), 1.0 / N, **f64)       # backtest.py:161
+    value = torch.full((P,), float(config.initial_capital), **f64)
+    hist = torch.empty((P, max(S, 1), 4), **f64)
+    metrics = torch.empty((P, 5), **f64)
+    L = _lib.load()
+    bd = _lib.BacktestDesc(P, N, max(S, 1), float(config.cost_coeff))
+    md = _mv_desc(P, N, H, strategy.mpc_config, False)
+    with torch.cuda.device(dev):
+        sh = _lib.stream_handle(dev)
+        if persistent is None or persistent:
+            rc = L.kmpc_markowitz_run(ctypes.byref(bd), ctypes.byref(md), pp.u, 0, 0, None, None, None, None, 0,
+                                      None, None, None, None, None, None, None, 0, sh)   # (shape check only)
+            if rc == _lib.KMPC_ERR_UNSUPPORTED and persistent is None:
+                persistent = False
+            elif rc == _lib.KMPC_ERR_UNSUPPORTED:
+                raise ValueError("persistent=True: no persistent Markowitz kernel for this shape")
+            else:
+                _lib.check(rc)
+                persistent = True
+        if persistent and P and S:
+            target = torch.empty((P, N), **f64)
+            status = torch.zeros((P,), dtype=torch.int32, device=dev)
+            objv = torch.empty((P,), **f64)
+            nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(md)))
+            ws = _workspace(dev, nws) if nws else None
+            for k0, n, mu, sigma, valid, rr, n_real in _markowitz_chunks(pp, lookback_window):
+                _lib.check(L.kmpc_markowitz_run(
+                    ctypes.byref(bd), ctypes.byref(md), pp.u, k0, n, mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(),
+                    rr.data_ptr() if rr is not None else None, n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(),
+                    target.data_ptr(), status.data_ptr(), objv.data_ptr(), ws.data_ptr() if ws is not None else None,
+                    nws, sh))
+        elif P and S:
+            for k0, n, mu, sigma, valid, rr, n_real in _markowitz_chunks(pp, lookback_window):
+                for k in range(n):
+                    W0, _, _ = solve_mpc_mean_variance_batched(w, mu[k], sigma[k], strategy.mpc_config)
+                    W0 = torch.where((valid[k] == 0).unsqueeze(1), w, W0)   # baselines.py:76-78: hold
+                    _lib.check(L.kmpc_backtest_step(ctypes.byref(bd), k0 + k, W0.data_ptr(),
+                                                    rr[k].data_ptr() if k < n_real else None, w.data_ptr(),
+                                                    value.data_ptr(), hist.data_ptr(), sh))
+        if P and S:
+            _lib.check(L.kmpc_backtest_metrics(ctypes.byref(bd), hist.data_ptr(), metrics.data_ptr(), sh))
+    return _markowitz_out(hist, w, metrics, S, (P,))
+
+
+def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: BacktestConfig, mean, std,
+                        risk_aversions: Sequence[float], cost_coeffs: Sequence[float],
+                        bt_cost_coeffs: Optional[Sequence[float]] = None, n_rows: Optional[int] = None,
+                        lookback_window: int = 60) -> Dict[str, Any]:
+    """A hyper-parameter sweep of run_markowitz_lockstep: C configs (risk_aversion, the strategy's
+    cost_coeff, BacktestConfig.cost_coeff) over the same P paths, every step of every (config, path)
+    in kmpc_markowitz_sweep launches, one workgroup each. The moments depend on the path only: they
+    are computed once per chunk for the P paths and shared by the configs.
+
+    Args:
+        strategy: its allow_short, max_weight and horizon are used, equal across the configs; its
+            risk_aversion and cost_coeff are not.
+        obs, realized, config, mean, std, n_rows, lookback_window: as run_markowitz_lockstep.
+        risk_aversions, cost_coeffs: [C] each (ValueError on unequal lengths or none).
+        bt_cost_coeffs: the bookkeeping's cost_coeff per config (default config.cost_coeff for all).
+    A config with a negative or non-finite risk_aversion or cost_coeff holds its weights at every
+    step (turnover and cost 0); the others are not affected. Config j's rows equal
+    run_markowitz_lockstep with that config's parameters bit for bit.
+    Returns: the run_markowitz_lockstep dict with a leading config axis — portfolio_value / return /
+        turnover / cost [C, P, S], weights [C, P, N], metrics {name: [C, P]} — and "status" [C, P]
+        int32, the last step's solve status of each work item (0 after a held step).
+    """
+    ga =[float(v) for v in risk_aversions]
+    mc = [float(v) for v in cost_coeffs]
+    C = len(ga)
+    if C < 1:
+        raise ValueError("risk_aversions is empty")
+    if len(mc) != C:
+        raise ValueError(f"cost_coeffs has {len(mc)} entries for {C} risk_aversions")
+    btc = [float(config.cost_coeff)] * C if bt_cost_coeffs is None else [float(v) for v in bt_cost_coeffs]
+    if len(btc) != C:
+        raise ValueError(f"bt_cost_coeffs has {len(btc)} entries for {C} configs")
+    pp = _markowitz_paths(strategy, obs, realized, config, mean, std, n_rows)
+    P, N, H, S, dev = pp.P, pp.N, pp.H, pp.S, pp.dev
+    f64 = dict(dtype=torch.float64, device=dev)
+    w = torch.full((C, P, N), 1.0 / N, **f64)
+    value = torch.full((C, P), float(config.initial_capital), **f64)
+    hist = torch.empty((C, P, max(S, 1), 4), **f64)
+    metrics = torch.empty((C * P, 5), **f64)
+    L = _lib.load()
+    bd = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
+    md = _mv_desc(C * P, N, H, strategy.mpc_config, False)
+    if P and S:
+        with torch.cuda.device(dev):
+            sh = _lib.stream_handle(dev)
+            pg, pc, pb = (torch.tensor(v, **f64) for v in (ga, mc, btc))
+            target = torch.empty((C * P, N), **f64)
+            status = torch.zeros((C * P,), dtype=torch.int32, device=dev)
+            objv = torch.empty((C * P,), **f64)
+            nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(md)))
+            ws = _workspace(dev, nws) if nws else None
+            for k0, n, mu, sigma, valid, rr, n_real in _markowitz_chunks(pp, lookback_window):
+                _lib.check(L.kmpc_markowitz_sweep(
+                    ctypes.byref(bd), ctypes.byref(md), pp.u, C, pg.data_ptr(), pc.data_ptr(), pb.data_ptr(), k0, n,
+                    mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), rr.data_ptr() if rr is not None else None,
+                    n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(), target.data_ptr(), status.data_ptr(),
+                    objv.data_ptr(), ws.data_ptr() if ws is not None else None, nws, sh))
+            dm = _lib.BacktestDesc(C * P, N, max(S, 1), 0.0)
+            _lib.check(L.kmpc_backtest_metrics(ctypes.byref(dm), hist.data_ptr(), metrics.data_ptr(), sh))
+    out = _markowitz_out(hist, w, metrics, S, (C, P))
+    out["status"] = status.reshape(C, P) if P and S else torch.zeros((C, P), dtype=torch.int32, device=dev)
+    return out
+
+
+def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Sequence["MarkowitzStrategy"]) -> list:
+    """run_backtest(strategies[j], env, config) for C Markowitz strategies on one environment in one
+    sweep (run_markowitz_sweep with P = 1): the env-level counterpart of sweep_backtest. The
+    strategies may differ in risk_aversion and cost_coeff only (ValueError otherwise, before any
+    device work). Returns C DataFrames with the reference's columns (date, portfolio_value, return,
+    turnover, cost), the rebalance_freq quirk kept. An env without stats (custom de-standardisation)
+    runs run_backtest per strategy."""
+    strats = list(strategies)
+    if not strats:
+        raise ValueError("strategies is empty")
+    s0 = strats[0]
+    for j, s in enumerate(strats):
+        for name in ("allow_short", "max_weight"):
+            if getattr(s, name) != getattr(s0, name):
+                raise ValueError(f"strategies[{j}] differs from strategies[0] in {name}: a sweep varies "
+                                 "risk_aversion and cost_coeff only")
+        if int(s.mpc_config.horizon) != int(s0.mpc_config.horizon):
+            raise ValueError(f"strategies[{j}] differs from strategies[0] in horizon: a sweep varies "
+                             "risk_aversion and cost_coeff only")
+    st = _env_stats(env)
+    n = getattr(env, "n_assets", None)
+    if st is None or n is None:
+        return [run_backtest(s, env, config, verbose=False) for s in strats]
+    data = env.test_dataset.data
+    rets = env.destandardize_returns(env.extract_current_returns(data))
+    n_rows = len(env.test_dataset)
+    out = run_markowitz_sweep(s0, torch.as_tensor(data)[None], torch.as_tensor(rets)[None], config, st[0], st[1],
+                              [s.risk_aversion for s in strats], [s.cost_coeff for s in strats], n_rows=n_rows)
+    steps = range(0, n_rows - config.horizon, config.rebalance_freq)
+    dates = [env.test_dataset.dates[t] for t in steps]
+    cols = {k: out[k][:, 0].cpu().numpy() for k in ("portfolio_value", "return", "turnover", "cost")}
+    return [pd.DataFrame({"date": dates, **{k: v[j] for k, v in cols.items()}}) for j in range(len(strats))]
+
+
 __all__: Sequence[str] = ("DMDStrategy", "MarkowitzStrategy", "fit_dmd", "dmd_model_spec",
-                          "rolling_moments", "Strategy")
+                          "rolling_moments", "Strategy", "run_markowitz_lockstep", "run_markowitz_sweep",
+                          "sweep_backtest_markowitz")

@@ -246,4 +246,74 @@ int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int 
                                         (hipStream_t)stream);
 }
 
+int kmpc_rolling_moments_paths(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                               const float* mean, const float* std, const int* ts,
+                               double* mu, double* sigma, int* valid, void* stream) {
+    if (P < 0 || n_ts < 0 || T < 0 || N < 1 || lookback < 1 || ldz < N) return KMPC_ERR_INVALID;
+    if ((long long)P * n_ts > 0x7fffffffLL) return KMPC_ERR_INVALID;
+    if (P == 0 || n_ts == 0) return KMPC_OK;
+    if (!z || !mean || !std || !ts || !mu || !sigma || !valid) return KMPC_ERR_INVALID;
+    return kmpc::rolling_moments_paths_launch(P, n_ts, T, N, lookback, z, ldz, mean, std, ts, mu, sigma, valid,
+                                              (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// kmpc_markowitz_run (the batch is the paths) and kmpc_markowitz_sweep (configs x paths; the configs
+// carry gamma and the two cost coefficients, the descs' are not read). Every rule is decided before
+// any launch, the position limit's in kmpc_solve_mv_box's order.
+int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
+                    const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
+                    const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
+                    double* weights, double* value, double* hist, double* target, int* status, double* obj,
+                    void* workspace, size_t ws_bytes, void* stream) {
+    if (!bd || !d || bd->P < 0 || bd->N < 1 || bd->S < 1 || step0 < 0 || n_steps < 0 ||
+        step0 + n_steps > bd->S || n_real < 0 || n_real > n_steps || d->N != bd->N || d->H < 1 ||
+        d->return_full_W)
+        return KMPC_ERR_INVALID;
+    if (sweep && (n_cfg < 1 || (long long)n_cfg * bd->P > 0x7fffffffLL)) return KMPC_ERR_INVALID;
+    if (d->H > KMPC_MV_MAX_H || (long long)d->N * d->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    double u = 0.0;   // the active limit (0: the plain kernels)
+    if (max_weight != 0.0) {
+        if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+        if (d->allow_short) return KMPC_ERR_UNSUPPORTED;
+        if (max_weight < 1.0) {   // (>= 1: an inactive bound)
+            if (!((double)d->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
+            u = max_weight;
+        }
+    }
+    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
+    if (!mu || !sigma || !valid || !weights || !value || !hist || !target || !status || !obj ||
+        (n_real > 0 && !realized) || (sweep && (!gamma || !mv_cost || !bt_cost)))
+        return KMPC_ERR_INVALID;
+    return kmpc::mv_bt_launch(bd, d, u, sweep ? n_cfg : 0, gamma, mv_cost, bt_cost, step0, n_steps, mu, sigma, valid,
+                              realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
+                              (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kmpc_markowitz_run(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight, int step0,
+                       int n_steps, const double* mu, const double* sigma, const int* valid, const float* realized,
+                       int n_real, double* weights, double* value, double* hist, double* target, int* status,
+                       double* obj, void* workspace, size_t ws_bytes, void* stream) {
+    return markowitz_entry(false, bdesc, mvdesc, max_weight, 0, nullptr, nullptr, nullptr, step0, n_steps, mu, sigma,
+                           valid, realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
+                           stream);
+}
+
+int kmpc_markowitz_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight, int n_cfg,
+                         const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
+                         const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
+                         double* weights, double* value, double* hist, double* target, int* status, double* obj,
+                         void* workspace, size_t ws_bytes, void* stream) {
+    return markowitz_entry(true, bdesc, mvdesc, max_weight, n_cfg, gamma, mv_cost, bt_cost, step0, n_steps, mu, sigma,
+                           valid, realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
+                           stream);
+}
+
 }  // extern "C"

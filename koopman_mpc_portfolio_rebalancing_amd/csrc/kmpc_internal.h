@@ -45,5 +45,14 @@ int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma
 int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, int ldz, const float* mean,
                            const float* stdv, const int* ts, double* mu, double* sigma, int* valid,
                            hipStream_t stream);
+int rolling_moments_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                                 const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
+                                 int* valid, hipStream_t stream);
+// the Markowitz backtest: the run (n_cfg = 0) or the sweep of n_cfg configs
+int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
+                 const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
+                 const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
+                 double* weights, double* value, double* hist, double* target, int* status, double* obj,
+                 void* ws, size_t ws_bytes, hipStream_t stream);
 
 }  // namespace kmpc

@@ -1,5 +1,6 @@
-// kmpc_mv.hip — batched mean-variance MPC solve (replaces solve_mpc_mean_variance, mpc.py:119-184)
-// and the Markowitz rolling moments (MarkowitzStrategy.rebalance, baselines.py:70-88).
+// kmpc_mv.hip — batched mean-variance MPC solve (replaces solve_mpc_mean_variance, mpc.py:119-184),
+// the Markowitz rolling moments (MarkowitzStrategy.rebalance, baselines.py:70-88) and the Markowitz
+// backtest of P paths, every step of a path in one workgroup (mv_bt_kernel, further down).
 //
 // Program per window (mpc.py:128, 145-172):
 //   maximize  sum_t [ w_t . mu_t - gamma w_t' Sigma w_t ] - c sum_t ||w_t - w_{t-1}||_1
@@ -22,7 +23,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "kmpc_internal.h"
+#include "kmpc_bt_step.h"
 
 namespace kmpc {
 namespace {
@@ -464,16 +468,104 @@ __global__ void __launch_bounds__(MAXT) mv_ipm_kernel(MvArgs a) {
     }
 }
 
-// Markowitz moments (baselines.py:70-88) for window b at test index t = ts[b]:
-// r_s = z_s * std + mean (float32, data_finance.py:740-742) for the rows s of the last `lookback`
-// of [0, t]; mu = mean (float32, as np.mean of the float32 history), Sigma = np.cov (float64,
-// ddof 1) + 1e-6 I; valid[b] = (t + 1 >= 5) (baselines.py:76-78).
-__global__ void rolling_moments_kernel(int B, int T, int N, int lookback, const float* z, int ldz,
+// The Markowitz backtest (kmpc_markowitz_run / kmpc_markowitz_sweep; run_backtest with a
+// MarkowitzStrategy, backtest.py:133-219 and baselines.py:48-106, for P independent paths): one
+// workgroup per work item runs every step of its path back to back — the step's window
+// (mv_window, or the hold of baselines.py:76-78 where the step has fewer than 5 past rows) then the
+// step's bookkeeping (kmpc_bt_step.h, as kmpc_backtest_step) — as bt_kernel (kmpc_bt_run.h) does for
+// the log-utility rows. Work item q = j P + p (config j, path p; j = 0 in the run form): its state
+// rows are q's, the step's moments and realized row are read at the path p (shared by the configs).
+struct MvBt {
+    int P;                    // paths
+    int items;                // work items: P, or configs x P
+    int n_steps;              // steps run by this launch
+    int n_real;               // steps k < n_real have a realized row (later ones: no market move)
+    int nbt;                  // threads of the bookkeeping: bt_step_kernel's block size for this N
+    const double* mu;         // [n_steps, P, H, N]
+    const double* sigma;      // [n_steps, P, N, N]
+    const int* valid;         // [n_steps, P]
+    const float* realized;    // [n_steps, P, N] log-returns of each step's t + 1
+    const double* gamma;      // SWEEP: [C] device, the solve's gamma
+    const double* mv_cost;    // SWEEP: [C] device, the solve's cost_coeff
+    const double* bt_cost;    // SWEEP: [C] device, the bookkeeping's cost_coeff
+    bt::StepArgs st;          // st.k = the first step's history row; st.target = the W0 rows [items, N]
+};
+
+// a0: the solve's program; a0.wp = the weights [items, N] (each step's w_prev: the item's current,
+// drifted weights), a0.wout = r.st.target, a0.status / a0.obj [items]. Every window is solved as
+// window 0 of a per-item copy whose pointers are the item's rows. A held step reports status
+// optimal and obj NaN. SWEEP: a config outside the program (gamma < 0, cost_coeff < 0 or a
+// non-finite value; the host cannot see the values) gets a NaN parameter, which mv_window answers
+// with KMPC_STATUS_SOLVER_ERROR and the hold fallback at every step.
+template <bool GM, bool BOX, bool SWEEP>
+__device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int q, double* lds, double* red) {
+    const int N = a0.N, n = a0.N * a0.H;
+    int p = q;
+    double gj = a0.gamma, cj = a0.c, cb = r.st.c;
+    if constexpr (SWEEP) {
+        const int j = q / r.P;
+        p = q - j * r.P;
+        gj = r.gamma[j], cj = r.mv_cost[j];
+        if (!(gj >= 0.0) || !isfinite(gj)) gj = __builtin_nan("");
+        if (!(cj >= 0.0) || !isfinite(cj)) cj = __builtin_nan("");
+        cb = r.bt_cost[j];
+    }
+    const size_t PN = (size_t)r.P * N;
+    for (int k = 0; k < r.n_steps; ++k) {
+        const size_t kp = (size_t)k * r.P + p;
+        if (r.valid[kp]) {   // (one value per workgroup: mv_window's barriers stay uniform)
+            MvArgs a = a0;
+            a.gamma = gj; a.c = cj;
+            a.return_full = 0;
+            a.mu = r.mu + kp * n;
+            a.sigma = r.sigma + kp * N * N;
+            a.wp = a0.wp + (size_t)q * N;
+            a.wout = a0.wout + (size_t)q * N;
+            a.status = a0.status + q;
+            a.obj = a0.obj + q;
+            a.iters = nullptr;
+            mv_window<GM, BOX>(a, 0, lds);
+        } else {
+            for (int i = threadIdx.x; i < N; i += blockDim.x) a0.wout[(size_t)q * N + i] = a0.wp[(size_t)q * N + i];
+            if (threadIdx.x == 0) {
+                a0.status[q] = KMPC_STATUS_OPTIMAL;
+                a0.obj[q] = __builtin_nan("");
+            }
+        }
+        __syncthreads();   // W0 (st.target) of every thread, and the solve's LDS, done
+        bt::StepArgs st = r.st;
+        st.k = r.st.k + k;
+        st.c = cb;
+        st.realized = k < r.n_real ? r.realized + k * PN : nullptr;
+        bt::bt_step_body(st, q, p, red, r.nbt);
+        __syncthreads();   // the drifted weights are the next solve's w_prev
+    }
+}
+
+template <int MAXT, bool GM, bool BOX, bool SWEEP>
+__global__ void __launch_bounds__(MAXT) mv_bt_kernel(MvArgs a0, MvBt r) {
+    extern __shared__ double lds[];
+    __shared__ double red[4];   // the bookkeeping's reduction slots (nbt <= 256: four waves)
+    if (GM) {
+        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, SWEEP>(a0, r, q, lds, red);
+    } else {
+        mv_bt_item<false, BOX, SWEEP>(a0, r, blockIdx.x, lds, red);
+    }
+}
+
+// Markowitz moments (baselines.py:70-88) for window b = s P + p: test index t = ts[s] of panel p of
+// z [P, T, ldz] (kmpc_rolling_moments: P = 1, so b = s; kmpc_rolling_moments_paths: outputs
+// [n_ts, P, ...]): r_s = z_s * std + mean (float32, data_finance.py:740-742) for the rows s of the
+// last `lookback` of [0, t] of that panel; mu = mean (float32, as np.mean of the float32 history),
+// Sigma = np.cov (float64, ddof 1) + 1e-6 I; valid[b] = (t + 1 >= 5) (baselines.py:76-78).
+__global__ void rolling_moments_kernel(int P, int T, int N, int lookback, const float* zp, int ldz,
                                        const float* mean, const float* stdv, const int* ts,
                                        double* mu, double* sigma, int* valid) {
     extern __shared__ double ml[];   // [N] float64 means
     const int b = blockIdx.x;
-    const int t = ts[b];
+    const int sb = b / P;
+    const float* z = zp + (size_t)(b - sb * P) * T * ldz;
+    const int t = ts[sb];
     const int hi = min(t + 1, T), lo = max(0, hi - lookback), rows = hi - lo;
     if (threadIdx.x == 0) valid[b] = (t + 1 >= 5 && t < T) ? 1 : 0;
     // z * std + mean as two float32 roundings (torch's mul then add): no FMA contraction here
@@ -555,12 +647,70 @@ int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
+// kmpc_markowitz_run (n_cfg = 0) / kmpc_markowitz_sweep: the arguments are checked by the C ABI;
+// here the storage variant, the workspace and the launch.
+int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
+                 const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
+                 const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
+                 double* weights, double* value, double* hist, double* target, int* status, double* obj,
+                 void* ws, size_t ws_bytes, hipStream_t stream) {
+    const bool sweep = n_cfg > 0;
+    const int items = sweep ? n_cfg * bd->P : bd->P;
+    kmpc_mv_desc di = *d;
+    di.B = items;
+    MvArgs a;
+    a.B = items; a.N = d->N; a.H = d->H;
+    a.gamma = d->gamma; a.c = d->cost_coeff;
+    a.allow_short = d->allow_short;
+    a.max_iter = d->max_iter > 0 ? d->max_iter : 100;
+    a.tol = d->tol > 0.0 ? d->tol : 1e-10;
+    a.return_full = 0;
+    a.mu = mu; a.sigma = sigma; a.sigma_stride = (size_t)d->N * d->N; a.wp = weights;
+    a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr;
+    a.ws = (double*)ws; a.slab = mv_slab(d->N, d->H);
+    a.max_weight = max_weight;
+    MvBt r;
+    r.P = bd->P; r.items = items; r.n_steps = n_steps; r.n_real = n_real;
+    r.nbt = d->N >= 256 ? 256 : 64 * ((d->N + 63) / 64);   // (backtest_step_launch's block)
+    r.mu = mu; r.sigma = sigma; r.valid = valid; r.realized = realized;
+    r.gamma = gamma; r.mv_cost = mv_cost; r.bt_cost = bt_cost;
+    r.st.P = items; r.st.N = d->N; r.st.S = bd->S; r.st.k = step0; r.st.c = sweep ? 0.0 : bd->cost_coeff;
+    r.st.target = target; r.st.realized = nullptr; r.st.w = weights; r.st.value = value; r.st.hist = hist;
+    const bool box = max_weight > 0.0;
+    const int n = d->N * d->H;
+    const int nt = 64 * ((n + 63) / 64);   // >= r.nbt
+    const bool in_lds = mv_in_lds(d->N, d->H);
+    if (!in_lds) {
+        if (n > 1024 || mv_small_bytes(d->N, d->H) > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
+        if (!ws || ws_bytes < mv_workspace_bytes(&di)) return KMPC_ERR_WORKSPACE;
+    }
+    const dim3 grid(in_lds ? items : (items < MV_SLOTS ? items : MV_SLOTS));
+    const size_t lds = in_lds ? mv_lds_bytes(d->N, d->H) : mv_small_bytes(d->N, d->H);
+    const auto launch = [&](auto bx, auto sw) {
+        if (in_lds)
+            hipLaunchKernelGGL((mv_bt_kernel<128, false, decltype(bx)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
+        else
+            hipLaunchKernelGGL((mv_bt_kernel<1024, true, decltype(bx)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    if (box) { if (sweep) launch(T{}, T{}); else launch(T{}, F{}); }
+    else     { if (sweep) launch(F{}, T{}); else launch(F{}, F{}); }
+    return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
+}
+
+int rolling_moments_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                                 const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
+                                 int* valid, hipStream_t stream) {
+    hipLaunchKernelGGL(rolling_moments_kernel, dim3((unsigned)(n_ts * P)), dim3(256), sizeof(double) * N, stream, P,
+                       T, N, lookback, z, ldz, mean, stdv, ts, mu, sigma, valid);
+    return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
+}
+
 int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, int ldz, const float* mean,
                            const float* stdv, const int* ts, double* mu, double* sigma, int* valid,
                            hipStream_t stream) {
-    hipLaunchKernelGGL(rolling_moments_kernel, dim3(B), dim3(256), sizeof(double) * N, stream, B, T, N,
-                       lookback, z, ldz, mean, stdv, ts, mu, sigma, valid);
-    return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
+    return rolling_moments_paths_launch(1, B, T, N, lookback, z, ldz, mean, stdv, ts, mu, sigma, valid, stream);
 }
 
 }  // namespace kmpc

@@ -198,6 +198,18 @@ def solve_mpc_log_utility(
 
 # ---- mean-variance MPC (mpc.py:119-184) ------------------------------------------------------
 
+def _mv_desc(B: int, N: int, H: int, config: MPCConfig, full: bool) -> _lib.MvDesc:
+    d = _lib.MvDesc()
+    d.B, d.N, d.H = int(B), int(N), int(H)
+    d.gamma = float(config.gamma)
+    d.cost_coeff = float(config.cost_coeff)
+    d.allow_short = int(bool(config.allow_short))
+    d.max_iter = int(getattr(config, "mv_max_iter", 100))
+    d.tol = float(getattr(config, "mv_tol", 1e-10))
+    d.return_full_W = int(bool(full))
+    return d
+
+
 def solve_mpc_mean_variance_batched(
     current_weights: torch.Tensor,
     mu: torch.Tensor,
@@ -248,14 +260,7 @@ def solve_mpc_mean_variance_batched(
     status = torch.empty(B, dtype=torch.int32, device=dev)
     value = torch.empty(B, dtype=torch.float64, device=dev)
     iters = torch.empty(B, dtype=torch.int32, device=dev)
-    d = _lib.MvDesc()
-    d.B, d.N, d.H = int(B), int(N), int(H)
-    d.gamma = float(config.gamma)
-    d.cost_coeff = float(config.cost_coeff)
-    d.allow_short = int(bool(config.allow_short))
-    d.max_iter = int(getattr(config, "mv_max_iter", 100))
-    d.tol = float(getattr(config, "mv_tol", 1e-10))
-    d.return_full_W = int(bool(return_full))
+    d = _mv_desc(B, N, H, config, return_full)
     L = _lib.load()
     u = _box_limit(config, N)
     with torch.cuda.device(dev):
