@@ -15,6 +15,12 @@
 #ifndef KMPC_RS_ASM_F32   // the float32 phase's reduce-scatter exchanges written out
 #define KMPC_RS_ASM_F32 1
 #endif
+#ifndef KMPC_TRISOLVE_DPP_F32   // the Schur triangular solves' broadcast inside the FMA
+#define KMPC_TRISOLVE_DPP_F32 1
+#endif
+#ifndef KMPC_TRISOLVE_DPP_F64
+#define KMPC_TRISOLVE_DPP_F64 1
+#endif
 #include "kmpc_solve_kernel.h"
 #include "kmpc_bt_run.h"
 

@@ -500,6 +500,123 @@ __device__ __forceinline__ T gbcast(T v, int src) {
     }
 }
 
+// lsolve()'s Schur triangular solves with the broadcast inside the FMA (v_fmac_*_dpp row_newbcast, as
+// the LDL^T column above) instead of v_readlane into SGPRs and an FMA that reads them, per precision;
+// 0 keeps the v_readlane form. Whole-wave windows with 16 < KM <= 32: row r on lane r of wave 0, so
+// the rows sit on DPP rows 0 and 1 and a chain runs blocked over them (trisolve_fwd_dpp below).
+// Set per translation unit, as KMPC_SCHUR_BCAST_* (DESIGN §3.2a).
+#ifndef KMPC_TRISOLVE_DPP_F32
+#define KMPC_TRISOLVE_DPP_F32 0
+#endif
+#ifndef KMPC_TRISOLVE_DPP_F64
+#define KMPC_TRISOLVE_DPP_F64 0
+#endif
+// Steps j = J0, J0 + DJ, ... (CNT of them) of a substitution chain on the lanes of the DPP rows in
+// RM: x = fma(-l[j + LO], lane (j & 15) of the row, x), the row's lane taken from x itself (SELF: a
+// dependent chain, the two wait states a DPP read needs after a VALU write of its source before
+// every step) or from c (a block update: c is not written, so only the first chunk waits, LEAD).
+// The lane is an immediate, hence the template parameters; rows outside RM keep x.
+#define KMPC_TS_SELF(op, i) "\n\ts_nop 1\n\t" op " %[x], %[x], -%[l" #i "] row_newbcast:%[r" #i "] row_mask:%[rm] bank_mask:0xf"
+#define KMPC_TS_FROM(op, i) "\n\t" op " %[x], %[c], -%[l" #i "] row_newbcast:%[r" #i "] row_mask:%[rm] bank_mask:0xf"
+#define KMPC_TS_IN(i) [l##i] "v"(l[J0 + DJ * i + LO]), [r##i] "n"((J0 + DJ * i) & 15)
+#define KMPC_TS_SELF_CHUNKS(op)                                                                                     \
+    if constexpr (CNT == 8)                                                                                         \
+        asm(KMPC_TS_SELF(op, 0) KMPC_TS_SELF(op, 1) KMPC_TS_SELF(op, 2) KMPC_TS_SELF(op, 3) KMPC_TS_SELF(op, 4)     \
+            KMPC_TS_SELF(op, 5) KMPC_TS_SELF(op, 6) KMPC_TS_SELF(op, 7)                                             \
+            : [x] "+v"(x)                                                                                           \
+            : [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1), KMPC_TS_IN(2), KMPC_TS_IN(3), KMPC_TS_IN(4),              \
+              KMPC_TS_IN(5), KMPC_TS_IN(6), KMPC_TS_IN(7));                                                         \
+    else if constexpr (CNT == 4)                                                                                    \
+        asm(KMPC_TS_SELF(op, 0) KMPC_TS_SELF(op, 1) KMPC_TS_SELF(op, 2) KMPC_TS_SELF(op, 3)                         \
+            : [x] "+v"(x) : [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1), KMPC_TS_IN(2), KMPC_TS_IN(3));              \
+    else if constexpr (CNT == 2)                                                                                    \
+        asm(KMPC_TS_SELF(op, 0) KMPC_TS_SELF(op, 1) : [x] "+v"(x) : [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1));    \
+    else                                                                                                            \
+        asm(KMPC_TS_SELF(op, 0) : [x] "+v"(x) : [rm] "n"(RM), KMPC_TS_IN(0))
+#define KMPC_TS_FROM_CHUNKS(w, op)                                                                                  \
+    if constexpr (CNT == 8)                                                                                         \
+        asm(w KMPC_TS_FROM(op, 0) KMPC_TS_FROM(op, 1) KMPC_TS_FROM(op, 2) KMPC_TS_FROM(op, 3) KMPC_TS_FROM(op, 4)   \
+            KMPC_TS_FROM(op, 5) KMPC_TS_FROM(op, 6) KMPC_TS_FROM(op, 7)                                             \
+            : [x] "+v"(x)                                                                                           \
+            : [c] "v"(c), [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1), KMPC_TS_IN(2), KMPC_TS_IN(3), KMPC_TS_IN(4),  \
+              KMPC_TS_IN(5), KMPC_TS_IN(6), KMPC_TS_IN(7));                                                         \
+    else if constexpr (CNT == 4)                                                                                    \
+        asm(w KMPC_TS_FROM(op, 0) KMPC_TS_FROM(op, 1) KMPC_TS_FROM(op, 2) KMPC_TS_FROM(op, 3)                       \
+            : [x] "+v"(x)                                                                                           \
+            : [c] "v"(c), [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1), KMPC_TS_IN(2), KMPC_TS_IN(3));                \
+    else if constexpr (CNT == 2)                                                                                    \
+        asm(w KMPC_TS_FROM(op, 0) KMPC_TS_FROM(op, 1)                                                               \
+            : [x] "+v"(x) : [c] "v"(c), [rm] "n"(RM), KMPC_TS_IN(0), KMPC_TS_IN(1));                                \
+    else                                                                                                            \
+        asm(w KMPC_TS_FROM(op, 0) : [x] "+v"(x) : [c] "v"(c), [rm] "n"(RM), KMPC_TS_IN(0))
+template <int CNT, int J0, int DJ, int LO, int RM, bool SELF, bool LEAD, int KL>
+__device__ __forceinline__ void trisolve_chunk(float& x, float c, const float (&l)[KL]) {
+    if constexpr (SELF) { KMPC_TS_SELF_CHUNKS("v_fmac_f32_dpp"); }
+    else if constexpr (LEAD) { KMPC_TS_FROM_CHUNKS("s_nop 1", "v_fmac_f32_dpp"); }
+    else { KMPC_TS_FROM_CHUNKS("", "v_fmac_f32_dpp"); }
+}
+template <int CNT, int J0, int DJ, int LO, int RM, bool SELF, bool LEAD, int KL>
+__device__ __forceinline__ void trisolve_chunk(double& x, double c, const double (&l)[KL]) {
+    if constexpr (SELF) { KMPC_TS_SELF_CHUNKS("v_fmac_f64_dpp"); }
+    else if constexpr (LEAD) { KMPC_TS_FROM_CHUNKS("s_nop 1", "v_fmac_f64_dpp"); }
+    else { KMPC_TS_FROM_CHUNKS("", "v_fmac_f64_dpp"); }
+}
+#undef KMPC_TS_FROM_CHUNKS
+#undef KMPC_TS_SELF_CHUNKS
+#undef KMPC_TS_IN
+#undef KMPC_TS_FROM
+#undef KMPC_TS_SELF
+template <int J0, int N, int DJ, int LO, int RM, bool SELF, bool LEAD = true, int KL, class T>
+__device__ __forceinline__ void trisolve_steps(T& x, T c, const T (&l)[KL]) {
+    constexpr int CNT = N >= 8 ? 8 : (N >= 4 ? 4 : (N >= 2 ? 2 : 1));
+    if constexpr (N > 0) {
+        static_assert(J0 + LO >= 0 && J0 + LO < KL && J0 + DJ * (N - 1) + LO >= 0 && J0 + DJ * (N - 1) + LO < KL, "multipliers");
+        trisolve_chunk<CNT, J0, DJ, LO, RM, SELF, LEAD>(x, c, l);
+        trisolve_steps<J0 + DJ * CNT, N - CNT, DJ, LO, RM, SELF, false>(x, c, l);
+    }
+}
+// x's rows 0 and 1 -> (a, b): a carries row 0's lanes in both rows, b row 1's (one permlane16 swap
+// per dword; x was written by the asm FMACs, whose hazards the compiler does not pad: the two wait
+// states a lane read needs)
+template <class T>
+__device__ __forceinline__ void trisolve_rows(T& x, T& a, T& b) {
+    asm("s_nop 1" : "+v"(x));
+    a = x;
+    b = x;
+    swap16(a, b);
+}
+// Forward L y = rhs of lsolve() on DPP rows 0 and 1 (lane r owns row r, lf[j] = L_rj, zero for
+// j >= r): the steps j <= 14 inside row 0, y_0..15 into row 1 by one swap, row 1's lanes apply them
+// in ascending order, then the steps j >= 16 inside row 1. Every lane applies the multiply-adds of
+// the v_readlane form with a nonzero multiplier in that form's order, so on finite data the result
+// is bit-identical; steps whose multiplier is zero on a whole row (j = 15 on row 0, j >= 16 on row 0,
+// every step on the lanes past row 1) are not issued.
+template <int KM, class T>
+__device__ __forceinline__ void trisolve_fwd_dpp(T& x, const T (&lf)[KM - 1]) {
+    static_assert(KM > 17 && KM <= 32, "rows on DPP rows 0 and 1");
+    trisolve_steps<0, 15, 1, 0, 0x1, true>(x, x, lf);
+    T ca, cb;
+    trisolve_rows(x, ca, cb);
+    trisolve_steps<0, 16, 1, 0, 0x2, false>(x, ca, lf);
+    trisolve_steps<16, KM - 17, 1, 0, 0x2, true>(x, x, lf);
+}
+// Backward L^T q = y, the mirror (lb[j - 1] = L_jr, zero for j <= r): the steps j >= 17 inside row
+// 1, q_16.. into row 0 by one swap, row 0's lanes apply them in descending order, then the steps
+// j = 15..1 inside row 0.
+template <int KM, class T>
+__device__ __forceinline__ void trisolve_bwd_dpp(T& x, const T (&lb)[KM - 1]) {
+    static_assert(KM > 17 && KM <= 32, "rows on DPP rows 0 and 1");
+    trisolve_steps<KM - 1, KM - 17, -1, -1, 0x2, true>(x, x, lb);
+    T ca, cb;
+    trisolve_rows(x, ca, cb);
+    trisolve_steps<KM - 1, KM - 16, -1, -1, 0x1, false>(x, cb, lb);
+    trisolve_steps<15, 15, -1, -1, 0x1, true>(x, x, lb);
+}
+template <int KM, int GL, class T>
+constexpr bool trisolve_dpp() {
+    return GL == 64 && KM > 17 && KM <= 32 && (sizeof(T) == 4 ? KMPC_TRISOLVE_DPP_F32 != 0 : KMPC_TRISOLVE_DPP_F64 != 0);
+}
+
 #ifndef KMPC_OPAQUE_LANE
 #define KMPC_OPAQUE_LANE 1
 #endif
@@ -1353,7 +1470,8 @@ __device__ __forceinline__ void lsolve(const TH& T, Shared<HM, NWM, typename TH:
             // G = L D L^T with L unit lower, stored strictly lower (zero on and above the
             // diagonal), so every step is one unconditional FMA on every lane.
             // The L entries are loaded into registers before each chain (sched_barrier): the
-            // chain then waits on no LDS read, one v_readlane pair + one FMA per step.
+            // chain then waits on no LDS read, one v_readlane pair + one FMA per step (one DPP FMA
+            // per step in the units that set KMPC_TRISOLVE_DPP_*: trisolve_fwd_dpp / trisolve_bwd_dpp).
             // forward: L y = rhs (lane r uses row r of L)
             const int lr = lane < KM ? lane : 0;
             {
@@ -1362,8 +1480,12 @@ __device__ __forceinline__ void lsolve(const TH& T, Shared<HM, NWM, typename TH:
                 for (int j = 0; j < KM - 1; ++j) lf[j] = sh.G[lr * KM + j];
                 const Real gd = sh.gid[lr];
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (trisolve_dpp<KM, TH::GLN, Real>()) {
+                    trisolve_fwd_dpp<KM>(rhs, lf);
+                } else {
 #pragma unroll
-                for (int j = 0; j < KM - 1; ++j) rhs = fma(-lf[j], gbcast<TH::GLN>(rhs, j), rhs);
+                    for (int j = 0; j < KM - 1; ++j) rhs = fma(-lf[j], gbcast<TH::GLN>(rhs, j), rhs);
+                }
                 rhs *= gd;   // D^{-1}
             }
             // backward: L^T q = D^{-1} y (lane r uses column r of L: row-major L, contiguous)
@@ -1372,8 +1494,12 @@ __device__ __forceinline__ void lsolve(const TH& T, Shared<HM, NWM, typename TH:
 #pragma unroll
                 for (int j = 1; j < KM; ++j) lb[j - 1] = sh.G[j * KM + lr];
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (trisolve_dpp<KM, TH::GLN, Real>()) {
+                    trisolve_bwd_dpp<KM>(rhs, lb);
+                } else {
 #pragma unroll
-                for (int j = KM - 1; j > 0; --j) rhs = fma(-lb[j - 1], gbcast<TH::GLN>(rhs, j), rhs);
+                    for (int j = KM - 1; j > 0; --j) rhs = fma(-lb[j - 1], gbcast<TH::GLN>(rhs, j), rhs);
+                }
             }
             if (lane < KM) sh.bs[lane] = rhs;
         }
