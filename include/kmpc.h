@@ -70,7 +70,7 @@ extern "C" {
  *          and cvxpy raises (DCPError) instead of returning a status.
  * Workspace: always size it with kmpc_workspace_bytes(NULL, desc). It is 0 for windows of
  *          N <= 256 assets and H <= 10 periods (solved in registers); otherwise the large-window
- *          kernel keeps each window's interior-point state there: (22 HM + 128) (64 ceil(N / 64))
+ *          kernel keeps each window's interior-point state there: (21 HM + 128) (64 ceil(N / 64))
  *          doubles per window slot, HM = 10 for H <= 10 and 21 past it (the compiled horizon
  *          bound, not H), for min(B, 768) slots when N <= 256, min(B, 512) otherwise.
  *          The mixed-precision pair (AUTO at >= KMPC_MIXED_MIN_B windows, MIXED) keeps a 64 B record

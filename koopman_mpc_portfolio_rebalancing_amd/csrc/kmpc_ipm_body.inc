@@ -314,6 +314,7 @@
 
                 // ---- predictor (pass 0) and corrector (pass 1) share one Newton body ----
                 Real step = Real(0.0);
+                bool refine_far = false;   // the corrector aims far below REFINE_MU from above it (REFINE_SMU)
                 for (int pass = 0; pass < 2; ++pass) {
                     // predictor unrefined (it only sets the step estimate, sigma and the
                     // second-order term); corrector refined adaptively once mu <= REFINE_MU (_SHORT)
@@ -330,7 +331,8 @@
 #pragma unroll
                     for (int t = 0; t < HM; ++t) { park[t] = T.w[t]; park[HM + t] = T.s[t]; }
                     if constexpr (PARK) asm volatile("" :: "v"(&park[0]) : "memory");
-                    newton<HM, NWM>(T, sh, R, (PH == 1 || pass == 0 || mu > (T.hw ? REFINE_MU : REFINE_MU_SHORT)) ? 0 : args.n_refine,
+                    newton<HM, NWM>(T, sh, R,
+                                    (PH == 1 || pass == 0 || (mu > (T.hw ? REFINE_MU : REFINE_MU_SHORT) && !refine_far)) ? 0 : args.n_refine,
                                     pass == 0);
                     if constexpr (PARK) asm volatile("" :: "v"(&park[0]) : "memory");
 #pragma unroll
@@ -345,6 +347,9 @@
                     sg = sg * sg * sg;
                     if (T.hw && T.ht) sg = fmin(sg, Real(KMPC_SIGMA_CAP));
                     const Real smu = sg * mu;
+                    // (not on the C3 rung, whose outputs are pinned byte for byte: REFINE_SMU)
+                    if constexpr (PH != 1 && !Variant<HM, MAXT, EXACT, FL, CS, QL, GL>::C3)
+                        refine_far = mu <= Real(REFINE_MU_SHORT) && smu <= Real(REFINE_SMU);
                     Real DL1[HM], DL2[HM], DL3[HM];
                     T.dual_dirs_all(DL1, DL2, DL3);
 #pragma unroll

@@ -135,6 +135,23 @@ constexpr double REFINE_RTOL = KMPC_REFINE_RTOL;
 #endif
 constexpr double REFINE_MU = KMPC_REFINE_MU;
 constexpr double REFINE_MU_SHORT = KMPC_REFINE_MU_SHORT;
+// ... and, between REFINE_MU and REFINE_MU_SHORT, when the corrector's centring target sigma mu is at
+// or below this: one step then takes mu from just above REFINE_MU to two decades below it, and the
+// unrefined float64 direction of that step leaves a dual residual that the refined iterations after
+// it no longer remove before the factorisation breaks down. The N = 9, H = 9 case-7 window of
+// tests/solve_variants.py (window 5): mu 1.135e-6 -> 5.9e-9 in one step, dual residual 2.2e-7 after it
+// (long double: 4e-10), best merit 2.2e-7 > 1e-7: optimal_inaccurate in the packed kernel and in the
+// oracle's float64 build; with that corrector refined 9.6e-11 (measured on the oracle in float64),
+// optimal. The rule fires on few iterations: on 256 windows of the benchmark's shape and 32 of
+// configs[0]'s the oracle's refinement passes per Newton solve go from 0.204 to 0.206, same
+// iteration counts (REFINE_MU = 2e-6 instead: 0.222). The long-double oracle does not need it and
+// keeps its rule. So does the C3 rung (H = 10, 64 < N < 104, case 7; its mixed and path-persistent
+// forms): it is the benchmark's kernel and tests/test_c3_newton_gpu.py pins its outputs byte for
+// byte — with the rule, windows of the N = 65 and N = 103 batches there change bits.
+#ifndef KMPC_REFINE_SMU
+#define KMPC_REFINE_SMU 1e-8
+#endif
+constexpr double REFINE_SMU = KMPC_REFINE_SMU;
 
 __host__ __device__ constexpr int pow2_at_least(int x) {
     int p = 1;
