@@ -329,6 +329,38 @@ int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* s
                         double* weights, double* value, double* hist, double* target, int* status,
                         double* obj, void* stream);
 
+/* kmpc_backtest_run and kmpc_backtest_sweep with a per-asset position limit (added within ABI 0.7.0,
+ * see the version note at the end): every step's solve is kmpc_solve_box(sdesc, max_weight, ...)
+ * instead of kmpc_solve, run by the same path-persistent kernel around the box kernels' window body.
+ * The results are bit-identical to the loop of kmpc_solve_box and kmpc_backtest_step per step.
+ * max_weight is one value for every path and config. Arrays, layouts, n_real, chunked calls
+ * through step0 and the n_steps = 0 shape probe are those of kmpc_backtest_run / kmpc_backtest_sweep;
+ * the sweep's rule for a config with max_turnover[j] <= 0, mpc_cost[j] < 0 or a non-finite parameter
+ * (KMPC_STATUS_SOLVER_ERROR and the hold at every step) is kept, so both sweeps take the same
+ * configs; the run takes any cost_coeff >= 0 and max_turnover kmpc_solve_box takes.
+ * Return codes, all decided before any launch, in this order:
+ *   - whatever kmpc_backtest_run / _sweep rejects before looking at the shape's kernel (NULL
+ *     descriptors, P / S / the step range / n_real, sdesc->N != desc->N, n_cfg, sdesc as for
+ *     kmpc_solve, NULL arrays with work to do): the same code;
+ *   - max_weight NaN or <= 0: KMPC_ERR_INVALID;
+ *   - max_weight >= 1 without shorting is an inactive bound: the call IS kmpc_backtest_run / _sweep
+ *     with the same arguments (its return code, bit-identical results);
+ *   - N * max_weight <= 1 (an empty feasible set, or the single point 1/N): KMPC_ERR_INVALID;
+ *   - KMPC_ERR_UNSUPPORTED: allow_short != 0; N > 256 or H > 10; path == KMPC_PATH_LARGE;
+ *     precision == KMPC_PRECISION_MIXED; return_full_W != 0; N <= 32 (the box case has no packed
+ *     form: run the lock-step loop there);
+ *   - P == 0 or n_steps == 0: KMPC_OK, nothing run.
+ * Shapes: 32 < N <= 256 and every H from 1 to 10; float64 at every batch size. */
+int kmpc_backtest_run_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight,
+                          int step0, int n_steps, const float* yhat, const float* realized, int n_real,
+                          double* weights, double* value, double* hist,
+                          double* target, int* status, double* obj, void* stream);
+int kmpc_backtest_sweep_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight,
+                            int n_cfg, const double* mpc_cost, const double* max_turnover, const double* bt_cost,
+                            int step0, int n_steps, const float* yhat, const float* realized, int n_real,
+                            double* weights, double* value, double* hist,
+                            double* target, int* status, double* obj, void* stream);
+
 /* metrics [P,5]: Sharpe Ratio, Max Drawdown, Avg Turnover, Final Value, Total Return. */
 int kmpc_backtest_metrics(const kmpc_backtest_desc* desc, const double* hist, double* metrics,
                           void* stream);
@@ -475,7 +507,9 @@ const char* kmpc_strerror(int code);
    for the symbol (dlsym) rather than for a version. kmpc_solve_mv_box was added within 0.7.0 in the
    same way: a new function only, kmpc_mv_desc and every existing function unchanged.
    kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep were added within 0.7.0 in
-   the same way: three new functions, no struct, enum or existing function changed. */
+   the same way: three new functions, no struct, enum or existing function changed.
+   kmpc_backtest_run_box and kmpc_backtest_sweep_box were added within 0.7.0 in the same way: two new
+   functions, no struct, enum or existing function changed. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

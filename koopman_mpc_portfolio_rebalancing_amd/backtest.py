@@ -217,6 +217,17 @@ PREROLL_CHUNK = 65536   # windows per batched rollout of run_backtest_lockstep(p
 LOCKSTEP_GROUPS = 3
 LOCKSTEP_GROUPS_MAX_P = 1024
 
+# With a position limit (MPCConfig.max_weight) the default of run_backtest_lockstep takes the
+# path-persistent kernel (kmpc_backtest_run_box) up to this many paths and the per-step loop past it;
+# persistent=True takes the kernel at any P. Measured (tools/box_persistent_probe.py,
+# profiles/box_persistent.md: max_weight = 0.05, kernel / loop in k path-steps/s, median of 5,
+# alternating; the spread of either is below 1%): N = 40, H = 5: P = 64 160.0 / 138.8, 256
+# 628.0 / 498.4, 1,024 1,777.5 / 1,695.1, 2,048 1,891.3 / 1,883.3 (inside the spread), 4,096
+# 2,366.8 / 2,394.8 — the loop is ahead by 1.2% there, outside the spread. The C3 shape (N = 100,
+# H = 10) is ahead at every P measured: 51.8 / 44.2, 203.9 / 165.3, 367.0 / 362.2, 366.7 / 329.4 and
+# at 4,096 368.7 / 339.6.
+BOX_PERSISTENT_MAX_P = 2048
+
 
 def _prepare_paths(km: DeviceKoopman, obs, realized, config: BacktestConfig, mean, std, n_rows: Optional[int]):
     """The P paths of a device backtest (run_backtest_lockstep's obs, realized, mean, std, n_rows):
@@ -243,14 +254,15 @@ def _run_persistent(km: DeviceKoopman, pp, mpc_config: MPCConfig, entry, n_items
                     metrics) -> bool:
     """Every step of the paths pp (_prepare_paths) in launches of a path-persistent entry point, one
     per rollout chunk of PREROLL_CHUNK // P steps, then the metrics: n_items work items (P paths, or
-    configs x paths) with their state in w, value, hist. entry(sdesc, k0, n, ...) -> the code of
-    kmpc_backtest_run or kmpc_backtest_sweep, given the arguments the two share: from the solve
-    descriptor, then the step range on. False (nothing run) where the C ABI has no persistent kernel
-    for the shape, and with a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it
-    and the persistent kernel has no box form — the lock-step loop's solves go through kmpc_solve_box."""
+    configs x paths) with their state in w, value, hist. entry(u, sdesc, k0, n, ...) -> the code of
+    kmpc_backtest_run or kmpc_backtest_sweep (u = 0.0) or, with a position limit u
+    (MPCConfig.max_weight: kmpc_solve_desc cannot carry it), of kmpc_backtest_run_box or
+    kmpc_backtest_sweep_box, which take u after the solve descriptor; the other arguments are those
+    the four share: the solve descriptor, then the step range on. False (nothing run) where the C ABI
+    has no persistent kernel for the shape (with a limit: N <= 32 — the lock-step loop's solves go
+    through kmpc_solve_box there)."""
     P, T, N, S, H, dev = pp.P, pp.T, pp.N, pp.S, int(mpc_config.horizon), km.device
-    if _box_limit(mpc_config, N):
-        return False
+    u = _box_limit(mpc_config, N)
     sdesc = _solve_desc(n_items, N, H, mpc_config, False)
     target = torch.empty((n_items, N), dtype=torch.float64, device=dev)
     status = torch.empty((n_items,), dtype=torch.int32, device=dev)
@@ -258,7 +270,7 @@ def _run_persistent(km: DeviceKoopman, pp, mpc_config: MPCConfig, entry, n_items
     sh = _lib.stream_handle(dev)
 
     def call(k0, n, y, rr, n_real):
-        return entry(ctypes.byref(sdesc), k0, n, y, rr, n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(),
+        return entry(u, ctypes.byref(sdesc), k0, n, y, rr, n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(),
                      target.data_ptr(), status.data_ptr(), objv.data_ptr(), sh)
 
     rc = call(0, 0, None, None, 0)   # (shape check only)
@@ -312,8 +324,11 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
             path never waits for another path's window. Default: with prerollout, without graph or
             groups, wherever the C ABI has the kernel for the shape (the float64 constant-case
             kernels kmpc_solve would use for the per-step batch: the C3 shape, 32 < N <= 256 at
-            H = 5 / 10, and the packed N <= 32 shapes at H = 2 / 5 / 10 — one path per lane group);
-            bit-identical to the lock-step loop. Falls back to the loop where unsupported.
+            H = 5 / 10, and the packed N <= 32 shapes at H = 2 / 5 / 10 — one path per lane group;
+            with a position limit, MPCConfig.max_weight, the box kernels kmpc_solve_box would use:
+            32 < N <= 256 at every H <= 10, kmpc_backtest_run_box, by default up to
+            BOX_PERSISTENT_MAX_P paths); bit-identical to the lock-step loop. Falls back to the
+            loop where unsupported (persistent=True raises there).
     Returns: dict of device tensors — portfolio_value / return / turnover / cost [P, S] (the
         reference DataFrame columns), weights [P, N] (after the last step), metrics {name: [P]}.
     """
@@ -341,14 +356,19 @@ def run_backtest_lockstep(strategy: KoopmanMPCStrategy, obs, realized, config: B
     explicit = persistent
     if persistent is None:
         persistent = prerollout and not graph and groups_arg is None
+        if persistent and P > BOX_PERSISTENT_MAX_P and _box_limit(strategy.mpc_config, N):
+            persistent = False   # (the loop measured ahead there)
     if persistent and (graph or not prerollout):
         raise ValueError("persistent needs prerollout=True and graph=False")
 
     def run_persistent() -> bool:
-        """Every step of every path in kmpc_backtest_run launches (_run_persistent): False (nothing
-        run) where there is no persistent kernel for this shape."""
-        def entry(*a):
-            return L.kmpc_backtest_run(ctypes.byref(d), *a)
+        """Every step of every path in kmpc_backtest_run launches (kmpc_backtest_run_box with a
+        position limit; _run_persistent): False (nothing run) where there is no persistent kernel
+        for this shape."""
+        def entry(u, sdesc, *a):
+            if u:
+                return L.kmpc_backtest_run_box(ctypes.byref(d), sdesc, u, *a)
+            return L.kmpc_backtest_run(ctypes.byref(d), sdesc, *a)
 
         if _run_persistent(km, pp, strategy.mpc_config, entry, P, w, value, hist, metrics):
             return True
@@ -467,6 +487,8 @@ def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: Back
             of bt_cost_coeffs).
         mpc_configs: C MPCConfigs that differ in cost_coeff and max_turnover only (ValueError otherwise).
         bt_cost_coeffs: the bookkeeping's cost_coeff per config (default config.cost_coeff for all).
+    With a position limit (MPCConfig.max_weight, equal across the configs) the launches are
+    kmpc_backtest_sweep_box's: the box kernels, 32 < N <= 256 at every H <= 10.
     Configs the kernel cannot take (max_turnover <= 0 or a non-finite parameter: another constraint
     case; every config where the C ABI has no sweep kernel for the shape) run as one
     run_backtest_lockstep call each. Config j's rows equal run_backtest_lockstep(..., persistent=True)
@@ -498,16 +520,19 @@ def run_backtest_sweep(strategy: KoopmanMPCStrategy, obs, realized, config: Back
 
     def run_kernel() -> bool:
         """Every step of every (config, path) in kmpc_backtest_sweep launches (_run_persistent): False
-        (nothing run) where there is no sweep kernel for this shape. (A position limit, max_weight, is
-        equal across the configs: _sweep_configs.)"""
+        (nothing run) where there is no sweep kernel for this shape. A position limit, max_weight, is
+        equal across the configs (_sweep_configs): with one, kmpc_backtest_sweep_box."""
         d = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
         f64 = dict(dtype=torch.float64, device=dev)
         pc = torch.tensor([float(cfgs[j].cost_coeff) for j in kern], **f64)
         pt = torch.tensor([float(cfgs[j].max_turnover) for j in kern], **f64)
         pb = torch.tensor([btc[j] for j in kern], **f64)
 
-        def entry(sdesc, *a):
-            return L.kmpc_backtest_sweep(ctypes.byref(d), sdesc, Ck, pc.data_ptr(), pt.data_ptr(), pb.data_ptr(), *a)
+        def entry(u, sdesc, *a):
+            par = (Ck, pc.data_ptr(), pt.data_ptr(), pb.data_ptr())
+            if u:
+                return L.kmpc_backtest_sweep_box(ctypes.byref(d), sdesc, u, *par, *a)
+            return L.kmpc_backtest_sweep(ctypes.byref(d), sdesc, *par, *a)
 
         return _run_persistent(km, pp, cfgs[0], entry, Ck * P, w, value, hist, metrics)
 

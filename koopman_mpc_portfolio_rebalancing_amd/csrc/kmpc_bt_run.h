@@ -11,6 +11,9 @@
 // in kmpc_solve_c3.hip (the C3 kernel), kmpc_solve_hbt*.hip (the constant-case kernels of
 // kmpc_solve_h*_case.hip) and kmpc_solve_p*.hip (the packed ones); the sweep in units of its own
 // (kmpc_solve_c3sw.hip, kmpc_solve_hsw*.hip, kmpc_solve_psw*.hip) with the options of those.
+// The box form (kmpc_backtest_run_box, kmpc_backtest_sweep_box: a per-asset position limit) wraps the
+// body of the box kernels of kmpc_solve_box (launch_ipm_box) the same way, in kmpc_solve_hbtbox*.hip
+// (the run) and kmpc_solve_hswbox*.hip (the sweep), built with the options of kmpc_solve_hbox*.hip.
 #pragma once
 #include "kmpc_solve_kernel.h"
 #include "kmpc_bt_step.h"
@@ -47,16 +50,24 @@ __device__ __forceinline__ const T& first_of(const T& t) { return t; }
 // mpc_cost < 0, or either NaN) gets a NaN parameter, which the window body answers with
 // KMPC_STATUS_SOLVER_ERROR and the hold fallback (W0 = w_prev) at every step. In the packed form the
 // lane groups of one wave hold different configs: c and tau are per-lane values.
-template <int HM, int MAXT, bool EXACT, int FL, int CS, bool QL, int GL, int PH, class... Sw>
+// BOX (shadows the namespace constant the window body reads by name): the per-step solve is the box
+// kernel ipm_kernel<HM, MAXT, false, -1, CS, false, 64, 0, true> of launch_ipm_box, the limit in
+// a0.max_weight (one value for every work item). That kernel is the generic one: it reads the
+// constraint case, c and tau at run time, so its sweep form needs no constant case; a poisoned
+// config's NaN parameter ends in the same KMPC_STATUS_SOLVER_ERROR hold.
+template <int HM, int MAXT, bool EXACT, int FL, int CS, bool QL, int GL, int PH, bool BOX, class... Sw>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(HM <= KMPC_WPE2_HM ? 2 : 1)))
 bt_kernel(SolveArgs a0, BtRun r, Sw... sw_) {
     constexpr bool SWEEP = sizeof...(Sw) == 1;
     static_assert(PH == 0, "float64 windows");
-    static_assert(!SWEEP || FL == 7, "per-config parameters stay inside one constant case");
+    static_assert(!SWEEP || FL == 7 || BOX, "per-config parameters stay inside one constant case, or the generic box kernel");
+    static_assert(!BOX || (FL == -1 && !EXACT && GL == 64 && !QL), "box kernels: generic float64, whole waves");
     static_assert(GL == 64 || MAXT == 64, "lane groups pack one-wave blocks");
     using Real = double;
     constexpr int NWM = MAXT / WAVE;
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;   // work items per block
+    static_assert(sizeof(Shared<HM, NWM, Real>) * WPB + sizeof(double) * NWM +
+                      cold_bytes<HM, MAXT, CS, QL, GL, FL, Real, BOX>() <= 160 * 1024, "LDS of one workgroup");
     __shared__ Shared<HM, NWM, Real> shv[WPB];
     __shared__ double red[NWM];
     auto& sh = shv[grp<GL>()];
@@ -111,7 +122,7 @@ bt_kernel(SolveArgs a0, BtRun r, Sw... sw_) {
 }
 
 // the launch (BtLaunch: kmpc_solve_args.h)
-template <bool SWEEP, int HM, int MAXT, bool EXACT, int FL, int CS = MAXT, bool QL = false, int GL = 64>
+template <bool SWEEP, int HM, int MAXT, bool EXACT, int FL, int CS = MAXT, bool QL = false, int GL = 64, bool BOX = false>
 int launch_bt_one(const SolveArgs& a, const BtLaunch& l, hipStream_t stream) {
     BtRun r;
     r.n_steps = l.n_steps;
@@ -122,10 +133,10 @@ int launch_bt_one(const SolveArgs& a, const BtLaunch& l, hipStream_t stream) {
     r.st.target = a.wout; r.st.realized = nullptr; r.st.w = l.weights; r.st.value = l.value; r.st.hist = l.hist;
     SolveArgs s = a;
     s.wp = l.weights;   // each step's w_prev: the work item's current (drifted) weights
-    const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, double>();
+    const size_t lds = cold_bytes<HM, MAXT, CS, QL, GL, FL, double, BOX>();
     constexpr int WPB = GL == 64 ? 1 : 64 / GL;
     const auto launch = [&](auto... sw) {
-        hipLaunchKernelGGL((bt_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, 0, decltype(sw)...>), dim3((a.B + WPB - 1) / WPB),
+        hipLaunchKernelGGL((bt_kernel<HM, MAXT, EXACT, FL, CS, QL, GL, 0, BOX, decltype(sw)...>), dim3((a.B + WPB - 1) / WPB),
                            dim3(GL == 64 ? block_threads(a.N) : 64), lds, stream, s, r, sw...);
     };
     if constexpr (SWEEP)
@@ -161,6 +172,20 @@ int launch_bt_case(const SolveArgs& a, const BtLaunch& l, hipStream_t stream) {
 template <bool SWEEP>
 int launch_bt_c3(const SolveArgs& a, const BtLaunch& l, hipStream_t stream) {
     return launch_bt_one<SWEEP, 10, 128, true, 7, QL_CS, true>(a, l, stream);
+}
+// The box form (a.max_weight set): the kernel launch_ipm_box<HM> takes for the same N, H <= HM read
+// at run time
+template <int HM, bool SWEEP>
+int launch_bt_box(const SolveArgs& a, const BtLaunch& l, hipStream_t stream) {
+    const int nt = block_threads(a.N);
+    if (a.H > HM || nt > 256) return KMPC_ERR_UNSUPPORTED;
+#if KMPC_BOX_QLCS
+    if constexpr (HM == 10)
+        if (nt == 128 && a.N < QL_CS) return launch_bt_one<SWEEP, HM, 128, false, -1, QL_CS, false, 64, true>(a, l, stream);
+#endif
+    if (nt <= 64) return launch_bt_one<SWEEP, HM, 64, false, -1, 64, false, 64, true>(a, l, stream);
+    if (nt <= 128) return launch_bt_one<SWEEP, HM, 128, false, -1, 128, false, 64, true>(a, l, stream);
+    return launch_bt_one<SWEEP, HM, 256, false, -1, 256, false, 64, true>(a, l, stream);
 }
 
 }  // namespace kmpc

@@ -23,15 +23,16 @@ int check_solve(const kmpc_solve_desc* d) {
     return KMPC_OK;
 }
 
-// kmpc_backtest_run (the batch is the paths) and kmpc_backtest_sweep (the batch is configs x paths; the
-// configs carry c and tau, sdesc's are not read). l: the caller's arguments; P, S and cost come from desc.
-int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
-                   kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
+// The argument checks kmpc_backtest_run (the batch is the paths), kmpc_backtest_sweep (the batch is
+// configs x paths; the configs carry c and tau, sdesc's are not read) and their box forms share. l: the
+// caller's arguments; P, S and cost come from desc. sd: the solve descriptor of the launch's batch.
+int backtest_check(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
+                   kmpc::BtLaunch& l, const double* target, const int* status, const double* obj, kmpc_solve_desc& sd) {
     if (!desc || !sdesc || desc->P < 0 || desc->N < 1 || desc->S < 1 || l.step0 < 0 || l.n_steps < 0 ||
         l.step0 + l.n_steps > desc->S || l.n_real < 0 || l.n_real > l.n_steps || sdesc->N != desc->N)
         return KMPC_ERR_INVALID;
     if (sweep && (n_cfg < 1 || (long long)n_cfg * desc->P > 0x7fffffffLL)) return KMPC_ERR_INVALID;
-    kmpc_solve_desc sd = *sdesc;
+    sd = *sdesc;
     sd.B = sweep ? n_cfg * desc->P : desc->P;
     if (sweep) {
         sd.cost_coeff = 0.0;
@@ -44,7 +45,34 @@ int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_
          (sweep && (!l.mpc_cost || !l.max_turnover || !l.bt_cost))))
         return KMPC_ERR_INVALID;
     l.P = desc->P; l.S = desc->S; l.cost = desc->cost_coeff;
+    return KMPC_OK;
+}
+
+int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
+                   kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
+    kmpc_solve_desc sd;
+    const int rc = backtest_check(sweep, desc, sdesc, n_cfg, l, target, status, obj, sd);
+    if (rc) return rc;
     return kmpc::backtest_launch(desc, &sd, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
+}
+
+// kmpc_backtest_run_box and kmpc_backtest_sweep_box: every rule is decided before any launch (and
+// before the P == 0 / n_steps == 0 return), the limit's in kmpc_solve_box's order. N <= 32 has no box
+// form: those shapes' persistent kernels are the packed ones.
+int backtest_box_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight,
+                       int n_cfg, kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
+    kmpc_solve_desc sd;
+    const int rc = backtest_check(sweep, desc, sdesc, n_cfg, l, target, status, obj, sd);
+    if (rc) return rc;
+    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    if (max_weight >= 1.0 && !sd.allow_short)           // an inactive bound: the plain kernels
+        return kmpc::backtest_launch(desc, &sd, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
+    if (!((double)sd.N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
+    if (sd.allow_short) return KMPC_ERR_UNSUPPORTED;
+    if (sd.N > 256 || sd.H > 10) return KMPC_ERR_UNSUPPORTED;
+    if (sd.path == KMPC_PATH_LARGE || sd.precision == KMPC_PRECISION_MIXED || sd.return_full_W) return KMPC_ERR_UNSUPPORTED;
+    if (sd.N <= 32) return KMPC_ERR_UNSUPPORTED;
+    return kmpc::backtest_box_launch(desc, &sd, max_weight, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -178,6 +206,23 @@ int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* s
     const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
                               yhat, realized, weights, value, hist};
     return backtest_entry(true, desc, sdesc, n_cfg, l, target, status, obj, stream);
+}
+
+int kmpc_backtest_run_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight, int step0,
+                          int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
+                          double* value, double* hist, double* target, int* status, double* obj, void* stream) {
+    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, nullptr, nullptr, nullptr,
+                              yhat, realized, weights, value, hist};
+    return backtest_box_entry(false, desc, sdesc, max_weight, 0, l, target, status, obj, stream);
+}
+
+int kmpc_backtest_sweep_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight, int n_cfg,
+                            const double* mpc_cost, const double* max_turnover, const double* bt_cost, int step0,
+                            int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
+                            double* value, double* hist, double* target, int* status, double* obj, void* stream) {
+    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
+                              yhat, realized, weights, value, hist};
+    return backtest_box_entry(true, desc, sdesc, max_weight, n_cfg, l, target, status, obj, stream);
 }
 
 int kmpc_standardize(int T, int N, const double* log_returns, const double* mean, const double* std,

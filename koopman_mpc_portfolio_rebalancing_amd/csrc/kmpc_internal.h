@@ -20,6 +20,9 @@ int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* y
 struct BtLaunch;
 int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const BtLaunch& l,
                     double* target, int* status, double* obj, hipStream_t stream);
+// ... with the position limit max_weight in every step's solve (the box kernels)
+int backtest_box_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
+                        const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream);
 
 // kmpc_backtest.hip
 int gross_returns_launch(size_t n, const float* yhat, float* R, hipStream_t stream);

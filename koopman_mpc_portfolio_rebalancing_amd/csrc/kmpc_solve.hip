@@ -278,4 +278,20 @@ int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int
     return sweep ? run(std::true_type{}) : run(std::false_type{});
 }
 
+// kmpc_backtest_run_box (n_cfg = 0) and kmpc_backtest_sweep_box: the same launch with the per-asset
+// position limit w <= max_weight in every step's solve, the window body that of the box kernel
+// kmpc_solve_box runs for the shape (launch_bt_box). No plan: the box solve is one kernel family at
+// every batch size. The caller (kmpc_capi.hip) has checked the shape and the limit: no short,
+// 1 / N < max_weight < 1, 32 < N <= 256, H <= 10, float64, W0 only.
+int backtest_box_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
+                        const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream) {
+    if (bd->P == 0 || l.n_steps == 0) return KMPC_OK;
+    SolveArgs a = make_args(sd);
+    a.max_weight = max_weight;   // (shares mu_handoff's slot: the box kernels have no float32 phase)
+    a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
+    a.yhat = l.yhat; a.wp = l.weights;
+    if (n_cfg > 0) return by_horizon(a.H, [&](auto hm) { return launch_bt_box<decltype(hm)::value, true>(a, l, stream); });
+    return by_horizon(a.H, [&](auto hm) { return launch_bt_box<decltype(hm)::value, false>(a, l, stream); });
+}
+
 }  // namespace kmpc

@@ -164,6 +164,12 @@ template <int HM, bool SWEEP>
 int launch_bt_case(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 template <int HM, bool SWEEP>
 int launch_bt_packed(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
+// ... and of the box case (a.max_weight: the position limit, one value for every work item): the
+// kernel launch_ipm_box<HM> picks for the same N (kmpc_solve_hbtbox*.hip, kmpc_solve_hswbox*.hip). The
+// sweep's a.c and a.tau come per config from the device arrays here too; the constraint case is read
+// at run time (the generic kernel).
+template <int HM, bool SWEEP>
+int launch_bt_box(const SolveArgs& a, const BtLaunch& l, hipStream_t stream);
 // packed small-window kernels, 64 / GL windows per wave (kmpc_solve_p*.hip); KMPC_ERR_UNSUPPORTED
 // outside N <= 32, 3 H <= 32
 template <int HM>

@@ -2183,7 +2183,8 @@ __device__ __forceinline__ Real record_best(const TH& T, Reducer<HM, NWM, TH::GL
 // BOX: the box case, a per-asset position limit w <= args.max_weight (kmpc_solve_box; float64,
 // whole-wave windows, the generic constraint case only).
 // The window body (kmpc_ipm_body.inc) reads BOX by name: the kernels that include it without a box
-// form (the mixed, path-persistent and sweep kernels) see this constant, ipm_kernel its own parameter.
+// form (the mixed kernels) see this constant, ipm_kernel and the path-persistent kernels (bt_kernel,
+// kmpc_bt_run.h: run and sweep) their own parameter.
 constexpr bool BOX = false;
 // ... and the iterate handed from phase to phase on chip by the name hand: ipm_kernel and the
 // backtest kernels declare the empty form (Handoff::ON false: PH = 1 / 2 / 3 go through args.warm),

@@ -13,7 +13,8 @@ For every unit (<unit>.s in either directory) and every kernel in it the script 
 A kernel that moved to another unit (--moved simplex_kernel=kmpc_solve_simplex) is compared across
 the two units. A kernel that was renamed (--renamed bt_run_kernel=bt_kernel) is paired with the
 kernel whose demangled name is the same after the substitution — same parameter list, same template
-arguments or those plus an added trailing pack — and both names are reported. Prints a markdown
+arguments, those plus an added trailing pack, or those with one argument inserted — and both names
+are reported. Prints a markdown
 report; exit status 1 if any kernel present on both sides differs.
 """
 import argparse
@@ -88,6 +89,12 @@ def split_name(dem):
     return m.groups(default="") if m else (dem, "", "")
 
 
+def one_inserted(targs, t2):
+    """t2 is targs with one template argument inserted (a new parameter ahead of a trailing pack)"""
+    a, b = targs.split(", "), t2.split(", ")
+    return len(b) == len(a) + 1 and any(b[:i] + b[i + 1:] == a for i in range(len(b)))
+
+
 def renamed_to(k, renamed, candidates):
     """The symbol among candidates that kernel k is called after --renamed, or None"""
     for old, new in renamed.items():
@@ -97,7 +104,7 @@ def renamed_to(k, renamed, candidates):
         name = name.replace(old, new)
         for k2 in candidates:
             n2, t2, p2 = split_name(short(k2))
-            if n2 == name and p2 == params and (t2 == targs or t2.startswith(targs + ", ")):
+            if n2 == name and p2 == params and (t2 == targs or t2.startswith(targs + ", ") or one_inserted(targs, t2)):
                 return k2
     return None
 
