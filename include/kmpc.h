@@ -155,6 +155,42 @@ int kmpc_solve_box(const kmpc_solve_desc* desc, double max_weight,
                    int*          iters,    /* [B] or NULL */
                    void* stream);
 
+/* ---- ... at every shape kmpc_solve takes (added within ABI 0.7.0, see the version note at the
+ * end): kmpc_solve_box with a workspace, so that the limit reaches the windows the large-window
+ * kernel solves (N > 256 or H > 10, and path == KMPC_PATH_LARGE at any shape; N <= 1024, H <= 21).
+ * There the limit is the same barrier inside the large-window interior point — two more arrays in
+ * each window's workspace slab (the multiplier, the corrector's target); same arrays, statuses,
+ * stopping and fallback rules as kmpc_solve on that kernel. The relation to kmpc_solve_box is that
+ * of kmpc_solve_mv_ws to kmpc_solve_mv.
+ * Return codes, all decided before any launch (and before the B == 0 return), in this order:
+ *   - desc is checked as for kmpc_solve;
+ *   - max_weight NaN or <= 0: KMPC_ERR_INVALID;
+ *   - max_weight >= 1 without shorting is an inactive bound: the call IS kmpc_solve(desc, ...,
+ *     workspace, ws_bytes) — bit-identical results; the workspace is handed on, so an inactive
+ *     bound works at every shape;
+ *   - N * max_weight <= 1: KMPC_ERR_INVALID;
+ *   - allow_short != 0 or precision == KMPC_PRECISION_MIXED: KMPC_ERR_UNSUPPORTED;
+ *   - N <= 256, H <= 10 and path != KMPC_PATH_LARGE: the call IS kmpc_solve_box(desc, max_weight,
+ *     ...) — bit-identical results, the workspace is not read;
+ *   - path == KMPC_PATH_REGISTER or _REGISTER_UNPACKED with N > 256 or H > 10: KMPC_ERR_UNSUPPORTED;
+ *   - else the large-window box kernel: KMPC_ERR_WORKSPACE where workspace is NULL or ws_bytes is
+ *     below kmpc_solve_box_workspace_bytes(desc, max_weight); then B == 0 returns KMPC_OK; then NULL
+ *     arrays (iters may be NULL) are KMPC_ERR_INVALID.
+ * kmpc_solve_box_workspace_bytes returns 0 for an invalid descriptor or limit and for the
+ * unsupported combinations, kmpc_workspace_bytes(NULL, desc) for an inactive bound, 0 where
+ * kmpc_solve_box runs, and otherwise 8 (23 HM + 128) 64 ceil(N / 64) min(B, slots) bytes, HM = 10
+ * for H <= 10 and 21 past it, slots = 768 windows in flight for N <= 256 and 512 past it (the plain
+ * solve's slab of 21 arrays plus two). kmpc_workspace_bytes and kmpc_solve do not change. */
+size_t kmpc_solve_box_workspace_bytes(const kmpc_solve_desc* desc, double max_weight);
+int kmpc_solve_box_ws(const kmpc_solve_desc* desc, double max_weight,
+                      const float*  yhat,     /* [B,H,N] */
+                      const double* w_prev,   /* [B,N]   */
+                      double*       w_out,    /* [B,N] or [B,H,N] */
+                      int*          status,   /* [B] */
+                      double*       obj,      /* [B] */
+                      int*          iters,    /* [B] or NULL */
+                      void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- gross returns: R = np.exp(yhat) on float32, bit for bit as numpy 2.x evaluates it on x86-64
  * (mpc.py:55; the realized returns np.exp(r) - 1 of backtest.py:188 use the same function).
  * yhat and R are device arrays of n floats. */
@@ -509,7 +545,10 @@ const char* kmpc_strerror(int code);
    kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep were added within 0.7.0 in
    the same way: three new functions, no struct, enum or existing function changed.
    kmpc_backtest_run_box and kmpc_backtest_sweep_box were added within 0.7.0 in the same way: two new
-   functions, no struct, enum or existing function changed. */
+   functions, no struct, enum or existing function changed.
+   kmpc_solve_box_workspace_bytes and kmpc_solve_box_ws were added within 0.7.0 in the same way: two
+   new functions, no struct, enum or existing function changed (kmpc_solve_box keeps every return
+   code it had). */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

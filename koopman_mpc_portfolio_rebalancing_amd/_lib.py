@@ -38,7 +38,8 @@ EXPORTED_SYMBOLS = ("kmpc_solve", "kmpc_rollout", "kmpc_window", "kmpc_workspace
                     "kmpc_mv_workspace_bytes", "kmpc_gross_returns", "kmpc_backtest_run",
                     "kmpc_backtest_sweep", "kmpc_solve_box", "kmpc_solve_mv_box",
                     "kmpc_rolling_moments_paths", "kmpc_markowitz_run", "kmpc_markowitz_sweep",
-                    "kmpc_backtest_run_box", "kmpc_backtest_sweep_box")
+                    "kmpc_backtest_run_box", "kmpc_backtest_sweep_box", "kmpc_solve_box_workspace_bytes",
+                    "kmpc_solve_box_ws")
 
 PATH_AUTO, PATH_REGISTER, PATH_LARGE, PATH_REGISTER_UNPACKED = 0, 1, 2, 3   # kmpc_solve_desc.path
 PRECISION_AUTO, PRECISION_F64, PRECISION_MIXED = 0, 1, 2   # kmpc_solve_desc.precision
@@ -51,7 +52,8 @@ PACK_MIN_B = 512     # KMPC_PACK_MIN_B: AUTO packs N <= 32 windows 2-4 per wave 
 # KMPC_DTYPE_F32_F32MFMA), no layout change; 0.5.0 added kmpc_backtest_run;
 # 0.6.0 enum values only (KMPC_LATENT_SEQUENTIAL); 0.7.0 added kmpc_backtest_sweep; kmpc_solve_box
 # and kmpc_solve_mv_box, then kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep,
-# then kmpc_backtest_run_box and kmpc_backtest_sweep_box were added within 0.7.0 (new functions only: nothing a 0.7.0 caller uses changed); a 0.7.0 library
+# then kmpc_backtest_run_box and kmpc_backtest_sweep_box, then kmpc_solve_box_workspace_bytes and kmpc_solve_box_ws
+# were added within 0.7.0 (new functions only: nothing a 0.7.0 caller uses changed); a 0.7.0 library
 # built before them lacks the symbols, which load() reports
 ABI_VERSION = "0.7.0"
 
@@ -177,6 +179,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     L.kmpc_backtest_run_box.restype = ctypes.c_int
     L.kmpc_backtest_sweep_box.argtypes = [bd, sd, cd, ci, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.kmpc_backtest_sweep_box.restype = ctypes.c_int
+    for name in ("kmpc_solve_box_workspace_bytes", "kmpc_solve_box_ws"):
+        if not hasattr(L, name):
+            raise KmpcError(f"{p} has no {name} (added within ABI {ABI_VERSION}): rebuild the library")
+    L.kmpc_solve_box_workspace_bytes.argtypes = [sd, cd]
+    L.kmpc_solve_box_workspace_bytes.restype = ctypes.c_size_t
+    L.kmpc_solve_box_ws.argtypes = [sd, cd, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.kmpc_solve_box_ws.restype = ctypes.c_int
     if path is None:
         _lib = L
     return L

@@ -75,6 +75,23 @@ int backtest_box_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_so
     return kmpc::backtest_box_launch(desc, &sd, max_weight, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
 }
 
+// Where kmpc_solve_box_ws sends a call (the rules it shares with its workspace query, in order)
+enum class BoxWs { ERROR, PLAIN, REGISTER, LARGE };
+BoxWs box_ws_route(const kmpc_solve_desc* desc, double max_weight, int& rc) {
+    rc = check_solve(desc);
+    if (rc) return BoxWs::ERROR;
+    rc = KMPC_ERR_INVALID;
+    if (!(max_weight > 0.0)) return BoxWs::ERROR;   // (NaN too)
+    if (max_weight >= 1.0 && !desc->allow_short) return BoxWs::PLAIN;   // an inactive bound
+    if (!((double)desc->N * max_weight > 1.0)) return BoxWs::ERROR;     // empty set or a single point
+    rc = KMPC_ERR_UNSUPPORTED;
+    if (desc->allow_short || desc->precision == KMPC_PRECISION_MIXED) return BoxWs::ERROR;
+    const bool small = desc->N <= 256 && desc->H <= 10;
+    if (small && desc->path != KMPC_PATH_LARGE) return BoxWs::REGISTER;
+    if (desc->path == KMPC_PATH_REGISTER || desc->path == KMPC_PATH_REGISTER_UNPACKED) return BoxWs::ERROR;
+    return BoxWs::LARGE;
+}
+
 }  // namespace
 
 extern "C" {
@@ -133,6 +150,33 @@ int kmpc_solve_box(const kmpc_solve_desc* desc, double max_weight, const float* 
     if (desc->B == 0) return KMPC_OK;
     if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
     return kmpc::solve_box_launch(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, (hipStream_t)stream);
+}
+
+size_t kmpc_solve_box_workspace_bytes(const kmpc_solve_desc* desc, double max_weight) {
+    int rc;
+    switch (box_ws_route(desc, max_weight, rc)) {
+        case BoxWs::PLAIN: return kmpc_workspace_bytes(nullptr, desc);
+        case BoxWs::LARGE: return kmpc::solve_bigbox_workspace_bytes(desc);
+        default: return 0;
+    }
+}
+
+int kmpc_solve_box_ws(const kmpc_solve_desc* desc, double max_weight, const float* yhat, const double* w_prev,
+                      double* w_out, int* status, double* obj, int* iters, void* workspace, size_t ws_bytes,
+                      void* stream) {
+    // every rule is decided before any launch (and before the B == 0 return)
+    int rc;
+    switch (box_ws_route(desc, max_weight, rc)) {
+        case BoxWs::ERROR: return rc;
+        case BoxWs::PLAIN: return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes, stream);
+        case BoxWs::REGISTER: return kmpc_solve_box(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, stream);
+        case BoxWs::LARGE: break;
+    }
+    if (!workspace || ws_bytes < kmpc::solve_bigbox_workspace_bytes(desc)) return KMPC_ERR_WORKSPACE;
+    if (desc->B == 0) return KMPC_OK;
+    if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
+    return kmpc::solve_bigbox_launch(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
+                                     (hipStream_t)stream);
 }
 
 /* Debug entry (not part of include/kmpc.h): kmpc_solve plus a per-iteration trace of problem 0,

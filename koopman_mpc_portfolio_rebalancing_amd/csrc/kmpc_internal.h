@@ -14,6 +14,11 @@ int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_pr
 
 int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
                      double* w_out, int* status, double* obj, int* iters, hipStream_t stream);
+// ... on the large-window box kernel (kmpc_solve_box_ws), and the workspace it needs
+size_t solve_bigbox_workspace_bytes(const kmpc_solve_desc* d);
+int solve_bigbox_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                        double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
+                        hipStream_t stream);
 
 // the path-persistent backtest: the run (n_cfg = 0) or the sweep of n_cfg configs (BtLaunch:
 // kmpc_solve_args.h)

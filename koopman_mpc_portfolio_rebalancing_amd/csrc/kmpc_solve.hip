@@ -247,6 +247,26 @@ int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* y
     });
 }
 
+// kmpc_solve_box_ws past the register box kernels (N > 256, H > 10 or KMPC_PATH_LARGE): the box form
+// of the large-window kernel, one launch per LAUNCH_MAX_B windows over the same slabs (the launches
+// are ordered on the stream). The caller has checked the shape and the limit as for solve_box_launch.
+size_t solve_bigbox_workspace_bytes(const kmpc_solve_desc* d) {
+    if (!d || d->B <= 0) return 0;
+    return big_box_ws_bytes(make_args(d));
+}
+
+int solve_bigbox_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                        double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
+                        hipStream_t stream) {
+    const SolveIO io = {yhat, w_prev, w_out, status, obj, iters};
+    return for_each_launch(d, io, [&](const kmpc_solve_desc& c, const SolveIO& s, bool) -> int {
+        SolveArgs a = make_args(c, s);
+        a.max_weight = max_weight;   // (shares mu_handoff's slot, which the large-window kernel does not read)
+        if (a.B == 0) return KMPC_OK;
+        return big_box_launch(a, ws, ws_bytes, stream);
+    });
+}
+
 // kmpc_backtest_run (n_cfg = 0) and kmpc_backtest_sweep (n_cfg >= 1 configs over the same bd->P
 // paths), one launch of the path-persistent kernel (kmpc_bt_run.h) in its run or sweep form. The
 // kernel exists where kmpc_solve sends the batch of sd->B windows (the caller has set it: P for the

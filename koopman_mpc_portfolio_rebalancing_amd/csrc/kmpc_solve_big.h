@@ -31,6 +31,14 @@
 // catastrophically, (v_t, v_t), is summed directly. Lr is clamped at 1e-14 (pi stays in the normal
 // range over 21 periods) and pi is centred (pi * 2^(-e/2), pi_H ~ 2^e); the clamp changes Q^{-1}
 // entries only where they are already below 1e-14 of the diagonal, i.e. at f64 rounding level.
+//
+// BOX (kmpc_solve_box_ws, instantiated in kmpc_solve_bigbox.hip): the per-asset position limit
+// w <= u = args.max_weight of the register box kernels — one more barrier on w, slack
+// u - w taken from the iterate, multiplier l5. Two more slab arrays (L5, and RC5: the corrector's
+// target without -smu); 1 / (u - w) is recomputed with the other slack reciprocals. Only per-asset
+// pieces move: the w row's multiplier is l1 - l5, Q's diagonal gains l5 / (u - w), the Newton
+// right-hand side rc5 / (u - w), the step length two ratio tests. Z, the Gram, the Schur system and
+// the LDS layout are those of the plain form, and every box line sits under if constexpr (BOX).
 #include "kmpc_solve_kernel.h"
 
 namespace kmpc {
@@ -97,8 +105,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 enum : int { A_W, A_S, A_L1, A_L2, A_L3, A_M, A_LR, A_IDD, A_RC1, A_RC2, A_RC3, A_DW, A_DS,
              A_BW, A_BS, A_X, A_Y, A_R0, A_R1, A_P, A_BP, N_ARR };
 
-__host__ __device__ inline size_t slab_doubles(int HM, int NP) {
-    return (size_t)N_ARR * HM * NP + 2 * (size_t)KP * NP;
+// ... and of the box form alone, after them (every array above keeps its offset)
+enum : int { A_L5 = N_ARR, A_RC5, N_ARR_BOX };
+
+__host__ __device__ inline size_t slab_doubles(int HM, int NP, bool box = false) {
+    return (size_t)(box ? N_ARR_BOX : N_ARR) * HM * NP + 2 * (size_t)KP * NP;
 }
 
 struct BigArgs {
@@ -135,10 +146,16 @@ template <int HM>
 constexpr int bs_doubles(int nw) { return (int)((sizeof(BigShared<HM>) - sizeof(double) * (NWX - nw) * KP + 7) / 8); }
 
 // state of one (t, i) with its slack-derived quantities (recomputed, never stored)
-struct St {
+// (BOX adds the limit's multiplier and 1 / (u - w); the plain form's struct is unchanged)
+template <bool BOX> struct StBox {};
+template <> struct StBox<true> { double l5, iu; };
+template <bool BOX>
+struct StT : StBox<BOX> {
     double w, s, d, l1, l2, l3, m;
     double iw, iz2, iz3, P, bma;
 };
+template <bool BOX> struct PreBox {};
+template <> struct PreBox<true> { double l5, rc5; };
 
 // 1 / x to ~1 ulp: v_rcp_f64 and two Newton steps (no division sequence)
 __device__ __forceinline__ double rcp(double x) {
@@ -185,7 +202,7 @@ struct Ref32 {
 #define KMPC_BIG_F32FAC 0
 #endif
 
-template <int HM, int FL>
+template <int HM, int FL, bool BOX = false>
 struct Win {
     const SolveArgs& a;
     BigShared<HM>& sh;
@@ -193,6 +210,7 @@ struct Win {
     int N, H, NP, nw, i;
     bool act;        // this thread's asset exists
     Case<FL> cs;
+    using St = StT<BOX>;
     double tau, isig, irsig, cs_c, wpi;
     int sbuf;
     __amdgpu_buffer_rsrc_t rs;   // the slab (wave-uniform base and size)
@@ -237,14 +255,15 @@ struct Win {
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b32(rs, 0u, 0u, 0)), r),
                                               rs, vo >> 1, so, 0);
     }
-    __device__ __forceinline__ double* lg(int j) const { return g + (size_t)N_ARR * HM * NP + (size_t)j * NP; }
-    __device__ __forceinline__ double* rg(int j) const { return g + (size_t)N_ARR * HM * NP + (size_t)(KP + j) * NP; }
+    static constexpr int NA = BOX ? N_ARR_BOX : N_ARR;   // per-(t, i) arrays ahead of the generators
+    __device__ __forceinline__ double* lg(int j) const { return g + (size_t)NA * HM * NP + (size_t)j * NP; }
+    __device__ __forceinline__ double* rg(int j) const { return g + (size_t)NA * HM * NP + (size_t)(KP + j) * NP; }
     __device__ __forceinline__ double wprev(int t) const { return t ? at(A_W, t - 1) : wpi; }
 
     // the stored state of (t, i) and the direction / targets the step, update and corrector
     // sweeps read with it: loaded one period ahead of its use, so that a wave keeps the next
     // period's loads in flight while it computes this one (the sweeps are load-latency bound)
-    struct Pre {
+    struct Pre : PreBox<BOX> {
         double w, s, l1, l2, l3, m, dw, ds, rc1, rc2, rc3, r0, r1;
     };
     // dir: + DW, DS; rc: + RC1..RC3; rr: + R0, R1 (a refinement pass's right-hand side)
@@ -259,6 +278,10 @@ struct Win {
         if (dir) { p.dw = at(A_DW, t); p.ds = at(A_DS, t); }
         if (rc) { p.rc1 = at(A_RC1, t); p.rc2 = at(A_RC2, t); p.rc3 = at(A_RC3, t); }
         if (rr) { p.r0 = at(A_R0, t); p.r1 = at(A_R1, t); }
+        if constexpr (BOX) {
+            p.l5 = at(A_L5, t);
+            if (rc) p.rc5 = at(A_RC5, t);
+        }
         return p;
     }
     __device__ __forceinline__ St st(const Pre& p, double wp) const {
@@ -269,6 +292,7 @@ struct Win {
         e.l2 = p.l2;
         e.l3 = p.l3;
         e.m = p.m;
+        if constexpr (BOX) e.l5 = p.l5;
         return derive(e, wp);
     }
     __device__ __forceinline__ St st(int t, double wp) const {
@@ -279,11 +303,13 @@ struct Win {
         e.l2 = at(A_L2, t);
         e.l3 = at(A_L3, t);
         e.m = mload(t);
+        if constexpr (BOX) e.l5 = at(A_L5, t);
         return derive(e, wp);
     }
     __device__ __forceinline__ St derive(St e, double wp) const {
         e.d = e.w - wp;
         e.iw = hw() ? rcp(e.w) : 0.0;
+        if constexpr (BOX) e.iu = rcp(a.max_weight - e.w);
         if (hs()) {
             e.iz2 = rcp(e.s - e.d);
             e.iz3 = rcp(e.s + e.d);
@@ -297,7 +323,8 @@ struct Win {
     }
     // dual residual rows (1)-(2) at period t (ipm_kernel dual_residual); l2n / l3n of period t + 1
     __device__ __forceinline__ void dres(int t, const St& e, double l2n, double l3n, double& rdw, double& rds) const {
-        rdw = -e.m * sh.iden[t] * isig - (e.l1 + (e.l3 - e.l2) - (l3n - l2n)) + sh.nu[t];
+        if constexpr (BOX) rdw = -e.m * sh.iden[t] * isig - ((e.l1 - e.l5) + (e.l3 - e.l2) - (l3n - l2n)) + sh.nu[t];
+        else rdw = -e.m * sh.iden[t] * isig - (e.l1 + (e.l3 - e.l2) - (l3n - l2n)) + sh.nu[t];
         rds = hs() ? cs_c - (e.l2 + e.l3 - sh.l4[t]) : 0.0;
     }
     // multipliers of a direction (complementarity rows with targets rc)
@@ -307,6 +334,10 @@ struct Win {
         dl2 = hs() ? (-rc2 - e.l2 * (ds - dd)) * e.iz2 : 0.0;
         dl3 = hs() ? (-rc3 - e.l3 * (ds + dd)) * e.iz3 : 0.0;
     }
+    // BOX: the limit's target (u - w) l5, and its multiplier along a direction (slack direction -dw,
+    // target rc5): dl5 = (-rc5 + l5 dw) / (u - w)
+    __device__ __forceinline__ double xl5(const St& e) const { return (a.max_weight - e.w) * e.l5; }
+    __device__ __forceinline__ double ddir5(const St& e, double rc5, double dw) const { return (-rc5 + e.l5 * dw) * e.iu; }
     // ds of (t, i) from the stored DS (P times the back-substituted s right-hand sides, summed over
     // the direction's solves): ds = DS - P rho pxa — the s elimination's last step, never stored
     __device__ __forceinline__ double dsv(int t, const St& e, double DSp) const {
@@ -386,11 +417,18 @@ struct Win {
         r2 = hs() ? b2 - smu : 0.0;
         r3 = hs() ? b3 - smu : 0.0;
     }
+    // BOX: the limit's corrector target b5 = (u - w) l5 + (-dw) dl5_aff to RC5, b5 - smu returned
+    __device__ __forceinline__ double corr_rc5(int t, const St& e, double dw, double smu) const {
+        const double rc5 = xl5(e);
+        const double b5 = rc5 - dw * ddir5(e, rc5, dw);
+        at(A_RC5, t) = b5;
+        return b5 - smu;
+    }
 };
 
 // period owners: den, iden, rp, rg4, rc4, iz4, rw from the slot totals of (R - 1).w, 1'w, 1's
-template <int HM, int FL>
-__device__ __forceinline__ void sums_owner(Win<HM, FL>& W) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void sums_owner(Win<HM, FL, BOX>& W) {
     auto& sh = W.sh;
     if (threadIdx.x < HM) {
         const int t = threadIdx.x;
@@ -409,8 +447,8 @@ __device__ __forceinline__ void sums_owner(Win<HM, FL>& W) {
 }
 
 // (1) period sums R.w, 1'w, 1's -> den, iden, rp, rg4, rc4, iz4, rw (period owners)
-template <int HM, int FL>
-__device__ __forceinline__ void ph_sums(Win<HM, FL>& W) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_sums(Win<HM, FL, BOX>& W) {
     for (int t = 0; t < W.H; ++t) {
         double mw = 0.0, w = 0.0, s = 0.0;
         if (W.act) {
@@ -428,8 +466,9 @@ __device__ __forceinline__ void ph_sums(Win<HM, FL>& W) {
 
 // (2) dual residual and complementarity sums, per-asset LDL^T of Q (LR, IDD), targets rc (RC*),
 // sum_i P per period -> rho, sr (owners). Returns mu (unscaled block sum) and rd (block max).
-template <int HM, int FL>
-__device__ __forceinline__ void ph_factor(Win<HM, FL>& W, double& mu_l, double& rd) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_factor(Win<HM, FL, BOX>& W, double& mu_l, double& rd) {
+    using St = typename Win<HM, FL, BOX>::St;
     auto& sh = W.sh;
     const bool hw = W.hw(), hs = W.hs(), ht = W.ht();
     const int H = W.H;
@@ -440,11 +479,12 @@ __device__ __forceinline__ void ph_factor(Win<HM, FL>& W, double& mu_l, double& 
     double W1c = 0.0, Ec = 0.0, pi = 0.0, lr = 0.0;
     double pm = 1.0;   // prod_{1<=k<=t} max(Lr_k, LR_FLOOR) = pm 2^pe (renormalised: no underflow)
     int pe = 0;
-    typename Win<HM, FL>::Pre pn{};   // the state of period t + 1, loaded at step t - 1
+    typename Win<HM, FL, BOX>::Pre pn{};   // the state of period t + 1, loaded at step t - 1
     if (W.act) {
         cur = W.st(0, W.wpi);
         if (H > 1) pn = W.pre(1, false, false);
         W1c = cur.l1 * cur.iw;
+        if constexpr (BOX) W1c += cur.l5 * cur.iu;
         Ec = hs ? 4.0 * (cur.l2 * cur.iz2) * (cur.l3 * cur.iz3) * cur.P : 0.0;
         pi = W1c + Ec;
     }
@@ -458,6 +498,7 @@ __device__ __forceinline__ void ph_factor(Win<HM, FL>& W, double& mu_l, double& 
                 nxt = W.st(pn, cur.w);
                 if (t + 2 < H) pn = W.pre(t + 2, false, false);
                 W1n = nxt.l1 * nxt.iw;
+                if constexpr (BOX) W1n += nxt.l5 * nxt.iu;
                 En = hs ? 4.0 * (nxt.l2 * nxt.iz2) * (nxt.l3 * nxt.iz3) * nxt.P : 0.0;
             }
             double rdw, rds;
@@ -466,6 +507,7 @@ __device__ __forceinline__ void ph_factor(Win<HM, FL>& W, double& mu_l, double& 
             const double r2 = hs ? (cur.s - cur.d) * cur.l2 : 0.0;
             const double r3 = hs ? (cur.s + cur.d) * cur.l3 : 0.0;
             mu_l += r1 + r2 + r3;
+            if constexpr (BOX) mu_l += W.xl5(cur);
             rd = fmax(rd, fmax(fabs(rdw), fabs(rds)));
             P = cur.P;
             W.fat(A_P, t) = cur.P;
@@ -516,8 +558,8 @@ __device__ __forceinline__ void ph_factor(Win<HM, FL>& W, double& mu_l, double& 
 // or factor sweeps — w double-buffered in the slab, or W written by the update that replaces the
 // best iterate, the norm as an extra reduction slot — measured slower on C5: 61.7 -> 64.2 / 62.4 ms,
 // 60 -> 74 / 63 spilled VGPRs in the load-latency-bound sweeps; r06, commit 518ee52)
-template <int HM, int FL>
-__device__ __forceinline__ void ph_record(Win<HM, FL>& W, double* wout, int tw) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_record(Win<HM, FL, BOX>& W, double* wout, int tw) {
     auto& sh = W.sh;
     double wprev = W.wpi, wn = 0.0;
     if (W.act) wn = W.at(A_W, 0);
@@ -540,8 +582,8 @@ __device__ __forceinline__ void ph_record(Win<HM, FL>& W, double* wout, int tw) 
 }
 
 // (3) Schur matrix: generators (slab) and the direct (v_t, v_t) sums, MFMA tiles of Lgen^T Rgen
-template <int HM, int FL>
-__device__ __forceinline__ void ph_gram(Win<HM, FL>& W) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_gram(Win<HM, FL, BOX>& W) {
     auto& sh = W.sh;
     const int H = W.H, K3 = 3 * H, N4 = (W.N + 3) & ~3;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
@@ -772,8 +814,9 @@ __device__ __forceinline__ void schur_solve(BigShared<HM>& sh, int H, const doub
 // (first) or added to DW, DS and sh.dnu.
 // corr: the first solve of the corrector — its targets rc + dx_aff dl_aff - smu are formed here
 // from the affine direction (DW, DS) and written back to RC* without -smu (no sweep of their own).
-template <int HM, int FL>
-__device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr = false, double smu = 0.0) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_lsolve(Win<HM, FL, BOX>& W, bool first, bool corr = false, double smu = 0.0) {
+    using St = typename Win<HM, FL, BOX>::St;
     auto& sh = W.sh;
     const bool hw = W.hw(), hs = W.hs(), ht = W.ht();
     const int H = W.H;
@@ -829,13 +872,14 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
         double y = 0.0;
         St cur{};
         double rc1c = 0.0, rc2c = 0.0, rc3c = 0.0, dwc = 0.0;
+        double rc5c = 0.0;   // BOX: the limit's target of the current period
         // bs of period t from its state and targets
         auto bsv = [&](int t, const St& e, double rc2, double rc3) -> double {
             const double b1 = -(W.cs_c - (e.l2 + e.l3 - sh.l4[t]));
             const double p23 = -rc2 * e.iz2 - rc3 * e.iz3;
             return b1 + p23 - sh.lb5[t] * sh.iz4[t];
         };
-        typename Win<HM, FL>::Pre pq{};   // period t + 1's state (+ the affine direction), loaded at step t - 1
+        typename Win<HM, FL, BOX>::Pre pq{};   // period t + 1's state (+ the affine direction), loaded at step t - 1
         double bsc = 0.0, gpc = 0.0, lrc = 0.0;
         if (W.act) {
             const auto p = W.pre(0, corr, false);
@@ -845,8 +889,10 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
             if (corr) {
                 dwc = p.dw;
                 W.corr_rc(0, cur, p, dwc, smu, rc1c, rc2c, rc3c);
+                if constexpr (BOX) rc5c = W.corr_rc5(0, cur, p.dw, smu);
             } else {
                 W.xl(cur, rc1c, rc2c, rc3c);
+                if constexpr (BOX) rc5c = W.xl5(cur);
             }
             bsc = bsv(0, cur, rc2c, rc3c);
             gpc = cur.bma * cur.P * bsc;
@@ -857,6 +903,7 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                 const bool nx = t + 1 < H;
                 St nxt = cur;
                 double rc1n = 0.0, rc2n = 0.0, rc3n = 0.0, dwn = 0.0, lrn = 0.0;
+                double rc5n = 0.0;
                 if (nx) {
                     const auto p = pq;
                     if (t + 2 < H) pq = W.pre(t + 2, corr, false);
@@ -865,14 +912,17 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                     if (corr) {
                         dwn = p.dw;
                         W.corr_rc(t + 1, nxt, p, dwn - dwc, smu, rc1n, rc2n, rc3n);
+                        if constexpr (BOX) rc5n = W.corr_rc5(t + 1, nxt, p.dw, smu);
                     } else {
                         W.xl(nxt, rc1n, rc2n, rc3n);
+                        if constexpr (BOX) rc5n = W.xl5(nxt);
                     }
                 }
                 double rdw, rds;
                 W.dres(t, cur, nx ? nxt.l2 : 0.0, nx ? nxt.l3 : 0.0, rdw, rds);
                 const double b0 = -rdw;
-                const double p1 = hw ? -rc1c * cur.iw : 0.0;
+                double p1 = hw ? -rc1c * cur.iw : 0.0;
+                if constexpr (BOX) p1 += rc5c * cur.iu;
                 const double p2 = -rc2c * cur.iz2;
                 const double p3 = -rc3c * cur.iz3;
                 const double pn = nx ? -rc3n * nxt.iz3 + rc2n * nxt.iz2 : 0.0;
@@ -885,6 +935,7 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                 pxv = cur.P * bsc;
                 cur = nxt;
                 rc1c = rc1n; rc2c = rc2n; rc3c = rc3n;
+                if constexpr (BOX) rc5c = rc5n;
                 dwc = dwn;
                 bsc = bsn;
                 gpc = gpn;
@@ -900,14 +951,17 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
         // refinement residual (!first)
         St cur{};
         double rc1c = 0.0, rc2c = 0.0, rc3c = 0.0, dwc = 0.0, r0c = 0.0, r1c = 0.0;
+        double rc5c = 0.0;   // BOX: the limit's target of the current period
         if (W.act) {
             const auto p = W.pre(0, corr, false, !first);
             cur = W.st(p, W.wpi);
             if (corr) {
                 dwc = p.dw;
                 W.corr_rc(0, cur, p, dwc, smu, rc1c, rc2c, rc3c);
+                if constexpr (BOX) rc5c = W.corr_rc5(0, cur, p.dw, smu);
             } else if (first) {
                 W.xl(cur, rc1c, rc2c, rc3c);
+                if constexpr (BOX) rc5c = W.xl5(cur);
             }
             r0c = p.r0;
             r1c = p.r1;
@@ -918,14 +972,17 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                 const bool nx = t + 1 < H;
                 St nxt = cur;
                 double rc1n = 0.0, rc2n = 0.0, rc3n = 0.0, dwn = 0.0, r0n = 0.0, r1n = 0.0;
+                double rc5n = 0.0;
                 if (nx) {
                     const auto p = W.pre(t + 1, corr, false, !first);
                     nxt = W.st(p, cur.w);
                     if (corr) {
                         dwn = p.dw;
                         W.corr_rc(t + 1, nxt, p, dwn - dwc, smu, rc1n, rc2n, rc3n);
+                        if constexpr (BOX) rc5n = W.corr_rc5(t + 1, nxt, p.dw, smu);
                     } else if (first) {
                         W.xl(nxt, rc1n, rc2n, rc3n);
+                        if constexpr (BOX) rc5n = W.xl5(nxt);
                     }
                     r0n = p.r0;
                     r1n = p.r1;
@@ -937,6 +994,7 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                     b0 = -rdw;
                     b1 = -rds;
                     p1 = hw ? -rc1c * cur.iw : 0.0;
+                    if constexpr (BOX) p1 += rc5c * cur.iu;
                     if (hs) {
                         p2 = -rc2c * cur.iz2;
                         p3 = -rc3c * cur.iz3;
@@ -955,6 +1013,7 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
                 rc1c = rc1n;
                 rc2c = rc2n;
                 rc3c = rc3n;
+                if constexpr (BOX) rc5c = rc5n;
                 dwc = dwn;
                 r0c = r0n;
                 r1c = r1n;
@@ -1163,8 +1222,9 @@ __device__ __forceinline__ void ph_lsolve(Win<HM, FL>& W, bool first, bool corr 
 // On exit: DW, DS, sh.dnu, sh.dz4, sh.dl4.
 // corr: this is the corrector — its targets (rc += dx_aff dl_aff - smu) are formed by the owners
 // (rc4) here and by the first solve's right-hand-side sweep (rc1..rc3).
-template <int HM, int FL>
-__device__ __forceinline__ void ph_newton(Win<HM, FL>& W, int n_refine, bool corr = false, double smu = 0.0) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_newton(Win<HM, FL, BOX>& W, int n_refine, bool corr = false, double smu = 0.0) {
+    using St = typename Win<HM, FL, BOX>::St;
     auto& sh = W.sh;
     const bool hs = W.hs(), ht = W.ht();
     const int H = W.H;
@@ -1226,6 +1286,11 @@ __device__ __forceinline__ void ph_newton(Win<HM, FL>& W, int n_refine, bool cor
                 W.dres(t, e, l2n, l3n, rdw, rds);
                 if (r == 0)
                     bn = fmax(bn, fmax(fmax(fabs(rdw), fabs(rds)), fmax(fabs(rc1), fmax(fabs(rc2), fabs(rc3)))));
+                if constexpr (BOX) {   // (the w row carries l1 - l5)
+                    const double rc5 = corr ? W.at(A_RC5, t) - smu : W.xl5(e);
+                    dl1 -= W.ddir5(e, rc5, dw);
+                    if (r == 0) bn = fmax(bn, fabs(rc5));
+                }
                 const double dl4 = ht ? (sh.b5[t] + sh.l4[t] * sh.sds[t]) * sh.iz4[t] : 0.0;
                 const double r0 = -rdw - (W.alpha(t, e.m) * sh.adw[t] - (dl1 + (dl3 - dl2) - (nl3 - nl2)) + sh.dnu[t]);
                 const double r1 = hs ? -rds + (dl2 + dl3 - dl4) : 0.0;
@@ -1265,8 +1330,9 @@ __device__ __forceinline__ void ph_newton(Win<HM, FL>& W, int n_refine, bool cor
 // (c0: ph_factor's mu sum) — the Mehrotra centring then needs no sweep of its own (ipm_kernel
 // max_step does the same).
 // pred: the predictor's direction, whose targets are x l (from the state, not stored)
-template <int HM, int FL>
-__device__ __forceinline__ double ph_step(Win<HM, FL>& W, double& c1, double& c2, bool pred, double smu = 0.0) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ double ph_step(Win<HM, FL, BOX>& W, double& c1, double& c2, bool pred, double smu = 0.0) {
+    using St = typename Win<HM, FL, BOX>::St;
     auto& sh = W.sh;
     const bool hw = W.hw(), hs = W.hs(), ht = W.ht();
     const int H = W.H;
@@ -1275,7 +1341,7 @@ __device__ __forceinline__ double ph_step(Win<HM, FL>& W, double& c1, double& c2
 #ifndef KMPC_BIG_PF2   // step length and update sweeps: loads two periods ahead (1) or one (0)
 #define KMPC_BIG_PF2 1
 #endif
-    typename Win<HM, FL>::Pre pn{}, pn2{};
+    typename Win<HM, FL, BOX>::Pre pn{}, pn2{};
     if (W.act) {
         pn = W.pre(0, true, !pred);
         if (KMPC_BIG_PF2 && H > 1) pn2 = W.pre(1, true, !pred);
@@ -1302,6 +1368,13 @@ __device__ __forceinline__ double ph_step(Win<HM, FL>& W, double& c1, double& c2
                 a = to_bound(e.w, dw, a); a = to_bound(e.l1, dl1, a);
                 c1 += e.w * dl1 + e.l1 * dw;
                 c2 += dw * dl1;
+            }
+            if constexpr (BOX) {   // u - w > 0 (direction -dw) and l5 > 0
+                const double dl5 = W.ddir5(e, pred ? W.xl5(e) : p.rc5 - smu, dw);
+                const double x5 = W.a.max_weight - e.w;
+                a = to_bound(x5, -dw, a); a = to_bound(e.l5, dl5, a);
+                c1 += x5 * dl5 - e.l5 * dw;
+                c2 -= dw * dl5;
             }
             if (hs) {
                 const double x2 = e.s - e.d, dx2 = ds - dd, x3 = e.s + e.d, dx3 = ds + dd;
@@ -1335,12 +1408,13 @@ __device__ __forceinline__ double ph_step(Win<HM, FL>& W, double& c1, double& c2
 
 // iterate update (the multiplier directions need the old state: w_{t-1} is carried), fused with
 // the next iteration's period sums (ph_sums) over the updated w, s
-template <int HM, int FL>
-__device__ __forceinline__ void ph_update(Win<HM, FL>& W, double step, double smu) {
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ void ph_update(Win<HM, FL, BOX>& W, double step, double smu) {
+    using St = typename Win<HM, FL, BOX>::St;
     auto& sh = W.sh;
     const int H = W.H;
     double wprev = W.wpi, dwp = 0.0;
-    typename Win<HM, FL>::Pre pn{}, pn2{};
+    typename Win<HM, FL, BOX>::Pre pn{}, pn2{};
     if (W.act) {
         pn = W.pre(0);
         if (KMPC_BIG_PF2 && H > 1) pn2 = W.pre(1);
@@ -1364,6 +1438,7 @@ __device__ __forceinline__ void ph_update(Win<HM, FL>& W, double step, double sm
             W.at(A_L1, t) = e.l1 + step * dl1;
             W.at(A_L2, t) = e.l2 + step * dl2;
             W.at(A_L3, t) = e.l3 + step * dl3;
+            if constexpr (BOX) W.at(A_L5, t) = e.l5 + step * W.ddir5(e, p.rc5 - smu, dw);
             wn = e.w + step * dw;
             sn = e.s + step * ds;
             W.at(A_W, t) = wn;
@@ -1384,8 +1459,8 @@ __device__ __forceinline__ void ph_update(Win<HM, FL>& W, double step, double sm
     sums_owner(W);
 }
 
-template <int HM, int FL>
-__device__ __forceinline__ int ipm_iterate(Win<HM, FL>& W, double* wout, int tw, double inv_ncon, double& best,
+template <int HM, int FL, bool BOX = false>
+__device__ __forceinline__ int ipm_iterate(Win<HM, FL, BOX>& W, double* wout, int tw, double inv_ncon, double& best,
                                         double& min_pr, int b) {
     auto& sh = W.sh;
     const SolveArgs& a = W.a;
@@ -1441,14 +1516,14 @@ __device__ __forceinline__ int ipm_iterate(Win<HM, FL>& W, double* wout, int tw,
     return it;
 }
 
-template <int HM, int MAXT, int FL>
+template <int HM, int MAXT, int FL, bool BOX = false>
 __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT >= 512 ? KMPC_BIG_WPE : 1))) ipm_big(BigArgs A) {
     static_assert(3 * HM <= KP - 1, "Schur system must fit one wave");
     constexpr int NWB = MAXT / WAVE;
     __shared__ double shraw[bs_doubles<HM>(NWB)];
     BigShared<HM>& sh = *reinterpret_cast<BigShared<HM>*>(shraw);
     const SolveArgs& a = A.s;
-    Win<HM, FL> W{a, sh, A.ws + (size_t)blockIdx.x * A.slab, a.N, a.H, A.NP, (int)(blockDim.x / WAVE),
+    Win<HM, FL, BOX> W{a, sh, A.ws + (size_t)blockIdx.x * A.slab, a.N, a.H, A.NP, (int)(blockDim.x / WAVE),
                   (int)threadIdx.x, (int)threadIdx.x < a.N};
     W.bind(A.slab);
     W.sbuf = 0;
@@ -1546,7 +1621,8 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
             } else {
                 // ---- initial point (as ipm_kernel / the oracle) ----
                 const double b0 = hw ? fmax(W.wpi, 0.0) : W.wpi;
-                const double w0 = 0.5 * b0 + 0.5 / N;
+                double w0 = 0.5 * b0 + 0.5 / N;
+                if constexpr (BOX) w0 = fmin(w0, 0.5 * (a.max_weight + 1.0 / N));
                 for (int t = 0; t < H; ++t) {
                     double s = 0.0;
                     if (W.act) {
@@ -1557,6 +1633,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
                         W.at(A_L1, t) = hw ? KMPC_INIT_MULT : 0.0;
                         W.at(A_L2, t) = hs ? KMPC_INIT_MULT : 0.0;
                         W.at(A_L3, t) = hs ? KMPC_INIT_MULT : 0.0;
+                        if constexpr (BOX) W.at(A_L5, t) = KMPC_INIT_MULT;
                     }
                     W.slot(t, s);
                 }
@@ -1568,7 +1645,7 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
                     sh.nu[t] = 0.0;
                 }
                 __syncthreads();
-                const int ncon = (hw ? H * N : 0) + (hs ? 2 * H * N : 0) + (ht ? H : 0);
+                const int ncon = (hw ? H * N : 0) + (hs ? 2 * H * N : 0) + (ht ? H : 0) + (BOX ? H * N : 0);
                 const double inv_ncon = 1.0 / (ncon > 0 ? ncon : 1);
                 double best = 1e300, min_pr = 1e300;
                 it = ipm_iterate(W, wout, tw, inv_ncon, best, min_pr, b);
@@ -1599,33 +1676,35 @@ __global__ void __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT 
 }
 
 // workspace bytes of the large-window launch
-template <int HM>
+template <int HM, bool BOX = false>
 size_t ws_bytes(const SolveArgs& a) {
     const int NP = WAVE * ((a.N + WAVE - 1) / WAVE);
-    return sizeof(double) * slab_doubles(HM, NP) * (size_t)slots_for(a.B, a.N);
+    return sizeof(double) * slab_doubles(HM, NP, BOX) * (size_t)slots_for(a.B, a.N);
 }
 
-template <int HM, int MAXT>
+// (BOX: the runtime-case kernel alone, as the register box kernels)
+template <int HM, int MAXT, bool BOX = false>
 int launch_t(const BigArgs& A, int slots, hipStream_t stream, int fl) {
-    if (fl == 7) hipLaunchKernelGGL((ipm_big<HM, MAXT, 7>), dim3(slots), dim3(A.NP), 0, stream, A);
+    if constexpr (BOX) hipLaunchKernelGGL((ipm_big<HM, MAXT, -1, true>), dim3(slots), dim3(A.NP), 0, stream, A);
+    else if (fl == 7) hipLaunchKernelGGL((ipm_big<HM, MAXT, 7>), dim3(slots), dim3(A.NP), 0, stream, A);
     else hipLaunchKernelGGL((ipm_big<HM, MAXT, -1>), dim3(slots), dim3(A.NP), 0, stream, A);
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
-template <int HM>
+template <int HM, bool BOX = false>
 int launch(const SolveArgs& a, void* ws, size_t ws_size, hipStream_t stream) {
     if (a.N > NWX * WAVE || a.H > HM) return KMPC_ERR_UNSUPPORTED;
-    if (!ws || ws_size < ws_bytes<HM>(a)) return KMPC_ERR_WORKSPACE;
+    if (!ws || ws_size < ws_bytes<HM, BOX>(a)) return KMPC_ERR_WORKSPACE;
     BigArgs A;
     A.s = a;
     A.NP = WAVE * ((a.N + WAVE - 1) / WAVE);
-    A.slab = slab_doubles(HM, A.NP);
+    A.slab = slab_doubles(HM, A.NP, BOX);
     A.ws = (double*)ws;
     const int slots = slots_for(a.B, a.N);
     const int fl = case_of(!a.allow_short, a.c > 0.0 || a.tau > 0.0, a.tau > 0.0);
-    if (A.NP <= 256) return launch_t<HM, 256>(A, slots, stream, fl);
-    if (A.NP <= 512) return launch_t<HM, 512>(A, slots, stream, fl);
-    return launch_t<HM, 1024>(A, slots, stream, fl);
+    if (A.NP <= 256) return launch_t<HM, 256, BOX>(A, slots, stream, fl);
+    if (A.NP <= 512) return launch_t<HM, 512, BOX>(A, slots, stream, fl);
+    return launch_t<HM, 1024, BOX>(A, slots, stream, fl);
 }
 
 }  // namespace big

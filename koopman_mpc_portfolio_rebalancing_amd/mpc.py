@@ -80,6 +80,20 @@ def _solve_desc(B: int, N: int, H: int, config: MPCConfig, full: bool) -> _lib.S
     return d
 
 
+def _box_route(d: _lib.SolveDesc) -> str:
+    """Which entry solves `d` under an active position limit: "large" (kmpc_solve_box_ws, the
+    large-window box kernel: MPCConfig.solver_path = 2, at every shape) or "register"
+    (kmpc_solve_box: N <= 256, H <= 10). The default path does not route by shape: a limit on a
+    larger window raises KmpcError, as kmpc_solve_box answers it with KMPC_ERR_UNSUPPORTED."""
+    if d.path == _lib.PATH_LARGE:
+        return "large"
+    if d.N > 256 or d.H > 10:
+        raise _lib.KmpcError(f"libkmpc call failed: unsupported shape ({_lib.KMPC_ERR_UNSUPPORTED}): the register box "
+                             f"kernels stop at N <= 256, H <= 10 (got N = {d.N}, H = {d.H}); set "
+                             f"MPCConfig.solver_path = 2 for the large-window box kernel")
+    return "register"
+
+
 def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     """A device buffer of at least nbytes for one call, from torch's caching allocator on the
     current stream: the block returns to the pool when the caller drops it and is handed out again
@@ -125,6 +139,15 @@ def solve_mpc_log_utility_batched(
     d = _solve_desc(B, N, H, config, return_full)
     L = _lib.load()
     u = _box_limit(config, N)
+    if u and _box_route(d) == "large":   # the large-window box kernel (its slabs: a workspace)
+        with torch.cuda.device(y.device):
+            nws = int(L.kmpc_solve_box_workspace_bytes(ctypes.byref(d), u))
+            ws = _workspace(y.device, nws)
+            rc = L.kmpc_solve_box_ws(ctypes.byref(d), u, y.data_ptr(), wp.data_ptr(), W.data_ptr(),
+                                     status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                                     ws.data_ptr(), nws, _lib.stream_handle(y.device))
+        _lib.check(rc)
+        return (W, status, value, iters) if with_iters else (W, status, value)
     if u:   # the position limit: the box case of the float64 register kernels (no workspace)
         with torch.cuda.device(y.device):
             rc = L.kmpc_solve_box(ctypes.byref(d), u, y.data_ptr(), wp.data_ptr(), W.data_ptr(),
