@@ -452,7 +452,10 @@ int kmpc_solve_mv_ws(const kmpc_mv_desc* desc, const double* mu, const double* s
  *   - max_weight >= 1 is an inactive bound: the call IS kmpc_solve_mv_ws with the same arguments,
  *     bit-identical results;
  *   - N * max_weight <= 1 (an empty feasible set, or the single point 1/N): KMPC_ERR_INVALID;
- *   - then the workspace rule of kmpc_solve_mv_ws (KMPC_ERR_WORKSPACE past H*N = 128 without one). */
+ *   - then the workspace rule of kmpc_solve_mv_ws (KMPC_ERR_WORKSPACE past H*N = 128 without one).
+ * This order is not kmpc_solve_box's: shorting is looked at before the inactive bound here, so
+ * allow_short with N * max_weight <= 1 is KMPC_ERR_UNSUPPORTED here and KMPC_ERR_INVALID there, and
+ * allow_short with max_weight >= 1 is KMPC_ERR_UNSUPPORTED here and the plain solve there. */
 int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double* mu, const double* sigma,
                       size_t sigma_stride, const double* w_prev, double* w_out, int* status, double* obj,
                       int* iters, void* workspace, size_t ws_bytes, void* stream);

@@ -32,15 +32,6 @@ STATUS_NAMES = {0: "optimal", 1: "optimal_inaccurate", 2: "infeasible", 3: "unbo
 KMPC_MV_MAX_HN = 1024    # mean-variance solve: H * N per workgroup (> 128: workspace-resident matrix)
 KMPC_MV_MAX_H = 16
 
-EXPORTED_SYMBOLS = ("kmpc_solve", "kmpc_rollout", "kmpc_window", "kmpc_workspace_bytes",
-                    "kmpc_backtest_step", "kmpc_backtest_metrics", "kmpc_standardize", "kmpc_strerror",
-                    "kmpc_version", "kmpc_solve_mv", "kmpc_rolling_moments", "kmpc_solve_mv_ws",
-                    "kmpc_mv_workspace_bytes", "kmpc_gross_returns", "kmpc_backtest_run",
-                    "kmpc_backtest_sweep", "kmpc_solve_box", "kmpc_solve_mv_box",
-                    "kmpc_rolling_moments_paths", "kmpc_markowitz_run", "kmpc_markowitz_sweep",
-                    "kmpc_backtest_run_box", "kmpc_backtest_sweep_box", "kmpc_solve_box_workspace_bytes",
-                    "kmpc_solve_box_ws")
-
 PATH_AUTO, PATH_REGISTER, PATH_LARGE, PATH_REGISTER_UNPACKED = 0, 1, 2, 3   # kmpc_solve_desc.path
 PRECISION_AUTO, PRECISION_F64, PRECISION_MIXED = 0, 1, 2   # kmpc_solve_desc.precision
 MIXED_MIN_B = 2048   # KMPC_MIXED_MIN_B: AUTO runs the mixed pair from this many windows per call
@@ -98,6 +89,44 @@ class BacktestDesc(ctypes.Structure):
                 ("cost_coeff", ctypes.c_double)]
 
 
+def _signatures() -> dict:
+    ci, cd, sz, vp, cs = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
+    sd, md, rd, bd = (ctypes.POINTER(t) for t in (SolveDesc, MvDesc, RolloutDesc, BacktestDesc))
+    return {
+        "kmpc_version": (cs, []),
+        "kmpc_strerror": (cs, [ci]),
+        "kmpc_workspace_bytes": (sz, [rd, sd]),
+        "kmpc_solve": (ci, [sd, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_solve_box": (ci, [sd, cd, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_solve_box_workspace_bytes": (sz, [sd, cd]),
+        "kmpc_solve_box_ws": (ci, [sd, cd, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_gross_returns": (ci, [sz, vp, vp, vp]),
+        "kmpc_rollout": (ci, [rd, vp, vp, vp, sz, vp]),
+        "kmpc_window": (ci, [rd, sd, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_standardize": (ci, [ci, ci, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_step": (ci, [bd, ci, vp, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_run": (ci, [bd, sd, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_sweep": (ci, [bd, sd, ci, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_run_box": (ci, [bd, sd, cd, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_sweep_box": (ci, [bd, sd, cd, ci, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_backtest_metrics": (ci, [bd, vp, vp, vp]),
+        "kmpc_solve_mv": (ci, [md, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "kmpc_mv_workspace_bytes": (sz, [md]),
+        "kmpc_solve_mv_ws": (ci, [md, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_solve_mv_box": (ci, [md, cd, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_rolling_moments": (ci, [ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_rolling_moments_paths": (ci, [ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "kmpc_markowitz_run": (ci, [bd, md, cd, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "kmpc_markowitz_sweep": (ci, [bd, md, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp,
+                                      vp, sz, vp]),
+    }
+
+
+# Every function of include/kmpc.h: name -> (restype, argtypes). The one list of the library's
+# symbols: load() binds from it and reports a missing one, EXPORTED_SYMBOLS is its names.
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
 _lib = None
 
 
@@ -110,82 +139,15 @@ def load(path: str | None = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise KmpcError(f"{p} not found: build it with `python -m koopman_mpc_portfolio_rebalancing_amd.build`")
     L = ctypes.CDLL(p)
-    vp, sz = ctypes.c_void_p, ctypes.c_size_t
-    L.kmpc_solve.argtypes = [ctypes.POINTER(SolveDesc), vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.kmpc_solve.restype = ctypes.c_int
-    L.kmpc_rollout.argtypes = [ctypes.POINTER(RolloutDesc), vp, vp, vp, sz, vp]
-    L.kmpc_rollout.restype = ctypes.c_int
-    L.kmpc_window.argtypes = [ctypes.POINTER(RolloutDesc), ctypes.POINTER(SolveDesc), vp, vp, vp, vp,
-                              vp, vp, vp, vp, sz, vp]
-    L.kmpc_window.restype = ctypes.c_int
-    L.kmpc_backtest_step.argtypes = [ctypes.POINTER(BacktestDesc), ctypes.c_int, vp, vp, vp, vp, vp, vp]
-    L.kmpc_backtest_step.restype = ctypes.c_int
-    L.kmpc_backtest_run.argtypes = [ctypes.POINTER(BacktestDesc), ctypes.POINTER(SolveDesc), ctypes.c_int,
-                                    ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_backtest_run.restype = ctypes.c_int
-    L.kmpc_backtest_sweep.argtypes = [ctypes.POINTER(BacktestDesc), ctypes.POINTER(SolveDesc), ctypes.c_int, vp, vp,
-                                      vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp,
-                                      vp]
-    L.kmpc_backtest_sweep.restype = ctypes.c_int
-    L.kmpc_backtest_metrics.argtypes = [ctypes.POINTER(BacktestDesc), vp, vp, vp]
-    L.kmpc_backtest_metrics.restype = ctypes.c_int
-    L.kmpc_standardize.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
-    L.kmpc_standardize.restype = ctypes.c_int
-    L.kmpc_solve_mv.argtypes = [ctypes.POINTER(MvDesc), vp, vp, sz, vp, vp, vp, vp, vp, vp]
-    L.kmpc_solve_mv.restype = ctypes.c_int
-    L.kmpc_solve_mv_ws.argtypes = [ctypes.POINTER(MvDesc), vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.kmpc_solve_mv_ws.restype = ctypes.c_int
-    L.kmpc_mv_workspace_bytes.argtypes = [ctypes.POINTER(MvDesc)]
-    L.kmpc_mv_workspace_bytes.restype = ctypes.c_size_t
-    ci = ctypes.c_int
-    L.kmpc_rolling_moments.argtypes = [ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_rolling_moments.restype = ctypes.c_int
-    L.kmpc_workspace_bytes.argtypes = [ctypes.POINTER(RolloutDesc), ctypes.POINTER(SolveDesc)]
-    L.kmpc_workspace_bytes.restype = ctypes.c_size_t
-    L.kmpc_gross_returns.argtypes = [sz, vp, vp, vp]
-    L.kmpc_gross_returns.restype = ctypes.c_int
-    L.kmpc_strerror.argtypes = [ctypes.c_int]
-    L.kmpc_strerror.restype = ctypes.c_char_p
-    L.kmpc_version.argtypes = []
     L.kmpc_version.restype = ctypes.c_char_p
     ver = L.kmpc_version().decode()
     if ver.split()[1:2] != [ABI_VERSION]:
         raise KmpcError(f"{p} reports {ver!r}; these bindings need ABI {ABI_VERSION}: rebuild the library")
-    if not hasattr(L, "kmpc_solve_box"):
-        raise KmpcError(f"{p} has no kmpc_solve_box (added within ABI {ABI_VERSION}): rebuild the library")
-    L.kmpc_solve_box.argtypes = [ctypes.POINTER(SolveDesc), ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_solve_box.restype = ctypes.c_int
-    if not hasattr(L, "kmpc_solve_mv_box"):
-        raise KmpcError(f"{p} has no kmpc_solve_mv_box (added within ABI {ABI_VERSION}): rebuild the library")
-    L.kmpc_solve_mv_box.argtypes = [ctypes.POINTER(MvDesc), ctypes.c_double, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz,
-                                    vp]
-    L.kmpc_solve_mv_box.restype = ctypes.c_int
-    for name in ("kmpc_rolling_moments_paths", "kmpc_markowitz_run", "kmpc_markowitz_sweep"):
+    for name, (restype, argtypes) in SIGNATURES.items():
         if not hasattr(L, name):
             raise KmpcError(f"{p} has no {name} (added within ABI {ABI_VERSION}): rebuild the library")
-    L.kmpc_rolling_moments_paths.argtypes = [ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_rolling_moments_paths.restype = ctypes.c_int
-    bd, md, cd = ctypes.POINTER(BacktestDesc), ctypes.POINTER(MvDesc), ctypes.c_double
-    L.kmpc_markowitz_run.argtypes = [bd, md, cd, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.kmpc_markowitz_run.restype = ctypes.c_int
-    L.kmpc_markowitz_sweep.argtypes = [bd, md, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
-                                       vp, vp, sz, vp]
-    L.kmpc_markowitz_sweep.restype = ctypes.c_int
-    for name in ("kmpc_backtest_run_box", "kmpc_backtest_sweep_box"):
-        if not hasattr(L, name):
-            raise KmpcError(f"{p} has no {name} (added within ABI {ABI_VERSION}): rebuild the library")
-    sd = ctypes.POINTER(SolveDesc)
-    L.kmpc_backtest_run_box.argtypes = [bd, sd, cd, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_backtest_run_box.restype = ctypes.c_int
-    L.kmpc_backtest_sweep_box.argtypes = [bd, sd, cd, ci, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.kmpc_backtest_sweep_box.restype = ctypes.c_int
-    for name in ("kmpc_solve_box_workspace_bytes", "kmpc_solve_box_ws"):
-        if not hasattr(L, name):
-            raise KmpcError(f"{p} has no {name} (added within ABI {ABI_VERSION}): rebuild the library")
-    L.kmpc_solve_box_workspace_bytes.argtypes = [sd, cd]
-    L.kmpc_solve_box_workspace_bytes.restype = ctypes.c_size_t
-    L.kmpc_solve_box_ws.argtypes = [sd, cd, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.kmpc_solve_box_ws.restype = ctypes.c_int
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     if path is None:
         _lib = L
     return L

@@ -256,7 +256,7 @@ def _run_persistent(km: DeviceKoopman, pp, mpc_config: MPCConfig, entry, n_items
     per rollout chunk of PREROLL_CHUNK // P steps, then the metrics: n_items work items (P paths, or
     configs x paths) with their state in w, value, hist. entry(u, sdesc, k0, n, ...) -> the code of
     kmpc_backtest_run or kmpc_backtest_sweep (u = 0.0) or, with a position limit u
-    (MPCConfig.max_weight: kmpc_solve_desc cannot carry it), of kmpc_backtest_run_box or
+    (MPCConfig.max_weight, mpc._box_limit), of kmpc_backtest_run_box or
     kmpc_backtest_sweep_box, which take u after the solve descriptor; the other arguments are those
     the four share: the solve descriptor, then the step range on. False (nothing run) where the C ABI
     has no persistent kernel for the shape (with a limit: N <= 32 — the lock-step loop's solves go

@@ -48,48 +48,56 @@ int backtest_check(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_
     return KMPC_OK;
 }
 
-int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
-                   kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
-    kmpc_solve_desc sd;
-    const int rc = backtest_check(sweep, desc, sdesc, n_cfg, l, target, status, obj, sd);
-    if (rc) return rc;
-    return kmpc::backtest_launch(desc, &sd, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
+// The position limit's own rule for the log-utility solve family (kmpc_solve_box, kmpc_solve_box_ws and
+// its workspace query, kmpc_backtest_run_box / _sweep_box), after the descriptor's checks: an error
+// code; or KMPC_OK with u = 0.0, an inactive bound (the plain entry runs); or KMPC_OK with the active
+// limit u. Which kernel family runs an active limit is the plan's answer (kmpc::box_family).
+// The one input this rule and mv_box_limit answer differently is allow_short with N * max_weight <= 1:
+// INVALID here (the empty set is found first), UNSUPPORTED there.
+int box_limit(const kmpc_solve_desc& d, double max_weight, double& u) {
+    u = 0.0;
+    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;                   // (NaN too)
+    if (max_weight >= 1.0 && !d.allow_short) return KMPC_OK;            // an inactive bound
+    if (!((double)d.N * max_weight > 1.0)) return KMPC_ERR_INVALID;     // empty set or a single point
+    if (d.allow_short) return KMPC_ERR_UNSUPPORTED;
+    u = max_weight;
+    return KMPC_OK;
 }
 
-// kmpc_backtest_run_box and kmpc_backtest_sweep_box: every rule is decided before any launch (and
-// before the P == 0 / n_steps == 0 return), the limit's in kmpc_solve_box's order. N <= 32 has no box
-// form: those shapes' persistent kernels are the packed ones.
-int backtest_box_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight,
-                       int n_cfg, kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
-    kmpc_solve_desc sd;
-    const int rc = backtest_check(sweep, desc, sdesc, n_cfg, l, target, status, obj, sd);
-    if (rc) return rc;
-    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
-    if (max_weight >= 1.0 && !sd.allow_short)           // an inactive bound: the plain kernels
-        return kmpc::backtest_launch(desc, &sd, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
-    if (!((double)sd.N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
-    if (sd.allow_short) return KMPC_ERR_UNSUPPORTED;
-    if (sd.N > 256 || sd.H > 10) return KMPC_ERR_UNSUPPORTED;
-    if (sd.path == KMPC_PATH_LARGE || sd.precision == KMPC_PRECISION_MIXED || sd.return_full_W) return KMPC_ERR_UNSUPPORTED;
-    if (sd.N <= 32) return KMPC_ERR_UNSUPPORTED;
-    return kmpc::backtest_box_launch(desc, &sd, max_weight, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
+// ... and for the mean-variance pair (kmpc_solve_mv_box; kmpc_markowitz_run / _sweep, where a
+// max_weight of 0 means none and does not come here), with the same three answers. Its order is its
+// own, shorting before the inactive bound: allow_short with N * max_weight <= 1 is UNSUPPORTED here
+// and INVALID in box_limit, and allow_short with max_weight >= 1 is UNSUPPORTED here, inactive there.
+int mv_box_limit(const kmpc_mv_desc& d, double max_weight, double& u) {
+    u = 0.0;
+    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;                   // (NaN too)
+    if (d.allow_short) return KMPC_ERR_UNSUPPORTED;
+    if (max_weight >= 1.0) return KMPC_OK;                              // an inactive bound
+    if (!((double)d.N * max_weight > 1.0)) return KMPC_ERR_INVALID;     // empty set or a single point
+    u = max_weight;
+    return KMPC_OK;
 }
 
-// Where kmpc_solve_box_ws sends a call (the rules it shares with its workspace query, in order)
-enum class BoxWs { ERROR, PLAIN, REGISTER, LARGE };
-BoxWs box_ws_route(const kmpc_solve_desc* desc, double max_weight, int& rc) {
-    rc = check_solve(desc);
-    if (rc) return BoxWs::ERROR;
-    rc = KMPC_ERR_INVALID;
-    if (!(max_weight > 0.0)) return BoxWs::ERROR;   // (NaN too)
-    if (max_weight >= 1.0 && !desc->allow_short) return BoxWs::PLAIN;   // an inactive bound
-    if (!((double)desc->N * max_weight > 1.0)) return BoxWs::ERROR;     // empty set or a single point
-    rc = KMPC_ERR_UNSUPPORTED;
-    if (desc->allow_short || desc->precision == KMPC_PRECISION_MIXED) return BoxWs::ERROR;
-    const bool small = desc->N <= 256 && desc->H <= 10;
-    if (small && desc->path != KMPC_PATH_LARGE) return BoxWs::REGISTER;
-    if (desc->path == KMPC_PATH_REGISTER || desc->path == KMPC_PATH_REGISTER_UNPACKED) return BoxWs::ERROR;
-    return BoxWs::LARGE;
+// The four kmpc_backtest_* entries; max_weight is null for the plain two. Every rule is decided before
+// any launch, the limit's (box_limit) before the P == 0 / n_steps == 0 return; an inactive bound IS the
+// plain call. Under a limit the plan has a persistent kernel for 32 < N <= 256, H <= 10, float64, W0
+// only, path != LARGE (N <= 32 has no box form: those shapes' persistent kernels are the packed ones).
+int backtest_entry(bool sweep, const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, const double* max_weight,
+                   int n_cfg, kmpc::BtLaunch l, double* target, int* status, double* obj, void* stream) {
+    kmpc_solve_desc sd;
+    int rc = backtest_check(sweep, desc, sdesc, n_cfg, l, target, status, obj, sd);
+    if (rc) return rc;
+    double u = 0.0;
+    if (max_weight && (rc = box_limit(sd, *max_weight, u))) return rc;
+    return kmpc::backtest_launch(desc, &sd, u, sweep ? n_cfg : 0, l, target, status, obj, (hipStream_t)stream);
+}
+
+// the caller's arrays of a kmpc_backtest_* entry (P, S and cost: backtest_check)
+kmpc::BtLaunch bt_args(int step0, int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
+                       double* value, double* hist, const double* mpc_cost = nullptr,
+                       const double* max_turnover = nullptr, const double* bt_cost = nullptr) {
+    return {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
+            yhat, realized, weights, value, hist};
 }
 
 }  // namespace
@@ -118,7 +126,7 @@ size_t kmpc_workspace_bytes(const kmpc_rollout_desc* rdesc, const kmpc_solve_des
     size_t bytes = 0;
     if (rdesc) bytes += kmpc::rollout_workspace_bytes(rdesc);
     if (rdesc && sdesc) bytes += align256(sizeof(float) * (size_t)rdesc->B * rdesc->H * rdesc->N);
-    if (sdesc && check_solve(sdesc) == KMPC_OK) bytes += align256(kmpc::solve_workspace_bytes(sdesc));
+    if (sdesc && check_solve(sdesc) == KMPC_OK) bytes += align256(kmpc::solve_workspace_bytes(sdesc, 0.0));
     return bytes;
 }
 
@@ -129,54 +137,54 @@ int kmpc_solve(const kmpc_solve_desc* desc, const float* yhat, const double* w_p
     if (rc) return rc;
     if (desc->B == 0) return KMPC_OK;
     if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
-    if (ws_bytes < kmpc::solve_workspace_bytes(desc)) return KMPC_ERR_WORKSPACE;
-    return kmpc::solve_launch(desc, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
+    if (ws_bytes < kmpc::solve_workspace_bytes(desc, 0.0)) return KMPC_ERR_WORKSPACE;
+    return kmpc::solve_launch(desc, 0.0, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
                               (hipStream_t)stream);
 }
 
+// The three limited solve entries decide every rule before any launch (and before the B == 0 return):
+// the descriptor, the limit (box_limit), then the family the plan names for an active limit.
 int kmpc_solve_box(const kmpc_solve_desc* desc, double max_weight, const float* yhat, const double* w_prev,
                    double* w_out, int* status, double* obj, int* iters, void* stream) {
-    // every rule is decided before any launch (and before the B == 0 return)
     int rc = check_solve(desc);
     if (rc) return rc;
-    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    double u;
+    if ((rc = box_limit(*desc, max_weight, u))) return rc;
     // an inactive bound: the plain solve, without a workspace (KMPC_ERR_WORKSPACE if it needs one)
-    if (max_weight >= 1.0 && !desc->allow_short)
-        return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, nullptr, 0, stream);
-    if (!((double)desc->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
-    if (desc->allow_short) return KMPC_ERR_UNSUPPORTED;
-    if (desc->N > 256 || desc->H > 10) return KMPC_ERR_UNSUPPORTED;
-    if (desc->path == KMPC_PATH_LARGE || desc->precision == KMPC_PRECISION_MIXED) return KMPC_ERR_UNSUPPORTED;
+    if (u == 0.0) return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, nullptr, 0, stream);
+    // (the large family needs the workspace only kmpc_solve_box_ws can hand over)
+    if (kmpc::box_family(desc, u) != kmpc::BoxFamily::REGISTER) return KMPC_ERR_UNSUPPORTED;
     if (desc->B == 0) return KMPC_OK;
     if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
-    return kmpc::solve_box_launch(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, (hipStream_t)stream);
+    return kmpc::solve_launch(desc, u, yhat, w_prev, w_out, status, obj, iters, nullptr, 0, (hipStream_t)stream);
 }
 
 size_t kmpc_solve_box_workspace_bytes(const kmpc_solve_desc* desc, double max_weight) {
-    int rc;
-    switch (box_ws_route(desc, max_weight, rc)) {
-        case BoxWs::PLAIN: return kmpc_workspace_bytes(nullptr, desc);
-        case BoxWs::LARGE: return kmpc::solve_bigbox_workspace_bytes(desc);
-        default: return 0;
-    }
+    double u;
+    if (check_solve(desc) || box_limit(*desc, max_weight, u)) return 0;
+    if (u == 0.0) return kmpc_workspace_bytes(nullptr, desc);
+    return kmpc::solve_workspace_bytes(desc, u);   // (0 for the register family, and for none)
 }
 
 int kmpc_solve_box_ws(const kmpc_solve_desc* desc, double max_weight, const float* yhat, const double* w_prev,
                       double* w_out, int* status, double* obj, int* iters, void* workspace, size_t ws_bytes,
                       void* stream) {
-    // every rule is decided before any launch (and before the B == 0 return)
-    int rc;
-    switch (box_ws_route(desc, max_weight, rc)) {
-        case BoxWs::ERROR: return rc;
-        case BoxWs::PLAIN: return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes, stream);
-        case BoxWs::REGISTER: return kmpc_solve_box(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, stream);
-        case BoxWs::LARGE: break;
+    int rc = check_solve(desc);
+    if (rc) return rc;
+    double u;
+    if ((rc = box_limit(*desc, max_weight, u))) return rc;
+    if (u == 0.0) return kmpc_solve(desc, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes, stream);
+    switch (kmpc::box_family(desc, u)) {
+        case kmpc::BoxFamily::NONE: return KMPC_ERR_UNSUPPORTED;
+        case kmpc::BoxFamily::REGISTER:
+            return kmpc_solve_box(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, stream);
+        case kmpc::BoxFamily::LARGE: break;
     }
-    if (!workspace || ws_bytes < kmpc::solve_bigbox_workspace_bytes(desc)) return KMPC_ERR_WORKSPACE;
+    if (!workspace || ws_bytes < kmpc::solve_workspace_bytes(desc, u)) return KMPC_ERR_WORKSPACE;
     if (desc->B == 0) return KMPC_OK;
     if (!yhat || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
-    return kmpc::solve_bigbox_launch(desc, max_weight, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
-                                     (hipStream_t)stream);
+    return kmpc::solve_launch(desc, u, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
+                              (hipStream_t)stream);
 }
 
 /* Debug entry (not part of include/kmpc.h): kmpc_solve plus a per-iteration trace of problem 0,
@@ -187,8 +195,8 @@ int kmpc_solve_trace(const kmpc_solve_desc* desc, const float* yhat, const doubl
     int rc = check_solve(desc);
     if (rc) return rc;
     if (desc->B == 0) return KMPC_OK;
-    if (ws_bytes < kmpc::solve_workspace_bytes(desc)) return KMPC_ERR_WORKSPACE;
-    return kmpc::solve_launch(desc, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
+    if (ws_bytes < kmpc::solve_workspace_bytes(desc, 0.0)) return KMPC_ERR_WORKSPACE;
+    return kmpc::solve_launch(desc, 0.0, yhat, w_prev, w_out, status, obj, iters, workspace, ws_bytes,
                               (hipStream_t)stream, trace);
 }
 
@@ -211,7 +219,7 @@ int kmpc_window(const kmpc_rollout_desc* rdesc, const kmpc_solve_desc* sdesc, co
     rc = kmpc::rollout_launch(rdesc, obs, y, workspace, rbytes, (hipStream_t)stream);
     if (rc) return rc;
     if (sdesc->B == 0) return KMPC_OK;
-    return kmpc::solve_launch(sdesc, y, w_prev, w_out, status, obj, iters, (char*)workspace + rbytes + ybytes,
+    return kmpc::solve_launch(sdesc, 0.0, y, w_prev, w_out, status, obj, iters, (char*)workspace + rbytes + ybytes,
                               ws_bytes - rbytes - ybytes, (hipStream_t)stream);
 }
 
@@ -238,35 +246,33 @@ int kmpc_backtest_step(const kmpc_backtest_desc* desc, int step, const double* t
 int kmpc_backtest_run(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int step0, int n_steps,
                       const float* yhat, const float* realized, int n_real, double* weights, double* value,
                       double* hist, double* target, int* status, double* obj, void* stream) {
-    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, nullptr, nullptr, nullptr,
-                              yhat, realized, weights, value, hist};
-    return backtest_entry(false, desc, sdesc, 0, l, target, status, obj, stream);
+    return backtest_entry(false, desc, sdesc, nullptr, 0, bt_args(step0, n_steps, yhat, realized, n_real, weights, value, hist),
+                          target, status, obj, stream);
 }
 
 int kmpc_backtest_sweep(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, int n_cfg,
                         const double* mpc_cost, const double* max_turnover, const double* bt_cost, int step0,
                         int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
                         double* value, double* hist, double* target, int* status, double* obj, void* stream) {
-    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
-                              yhat, realized, weights, value, hist};
-    return backtest_entry(true, desc, sdesc, n_cfg, l, target, status, obj, stream);
+    return backtest_entry(true, desc, sdesc, nullptr, n_cfg,
+                          bt_args(step0, n_steps, yhat, realized, n_real, weights, value, hist, mpc_cost, max_turnover, bt_cost),
+                          target, status, obj, stream);
 }
 
 int kmpc_backtest_run_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight, int step0,
                           int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
                           double* value, double* hist, double* target, int* status, double* obj, void* stream) {
-    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, nullptr, nullptr, nullptr,
-                              yhat, realized, weights, value, hist};
-    return backtest_box_entry(false, desc, sdesc, max_weight, 0, l, target, status, obj, stream);
+    return backtest_entry(false, desc, sdesc, &max_weight, 0, bt_args(step0, n_steps, yhat, realized, n_real, weights, value, hist),
+                          target, status, obj, stream);
 }
 
 int kmpc_backtest_sweep_box(const kmpc_backtest_desc* desc, const kmpc_solve_desc* sdesc, double max_weight, int n_cfg,
                             const double* mpc_cost, const double* max_turnover, const double* bt_cost, int step0,
                             int n_steps, const float* yhat, const float* realized, int n_real, double* weights,
                             double* value, double* hist, double* target, int* status, double* obj, void* stream) {
-    const kmpc::BtLaunch l = {/* P */ 0, n_steps, n_real, step0, /* S, cost */ 0, 0.0, mpc_cost, max_turnover, bt_cost,
-                              yhat, realized, weights, value, hist};
-    return backtest_box_entry(true, desc, sdesc, max_weight, n_cfg, l, target, status, obj, stream);
+    return backtest_entry(true, desc, sdesc, &max_weight, n_cfg,
+                          bt_args(step0, n_steps, yhat, realized, n_real, weights, value, hist, mpc_cost, max_turnover, bt_cost),
+                          target, status, obj, stream);
 }
 
 int kmpc_standardize(int T, int N, const double* log_returns, const double* mean, const double* std,
@@ -310,19 +316,20 @@ int kmpc_solve_mv_ws(const kmpc_mv_desc* desc, const double* mu, const double* s
 int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double* mu, const double* sigma,
                       size_t sigma_stride, const double* w_prev, double* w_out, int* status, double* obj,
                       int* iters, void* workspace, size_t ws_bytes, void* stream) {
-    // every rule is decided before any launch (and before the B == 0 return), in kmpc_solve_box's order
+    // every rule is decided before any launch (and before the B == 0 return): the descriptor as
+    // kmpc_solve_mv_ws, then the limit in mv_box_limit's order (not kmpc_solve_box's)
     if (!desc || desc->B < 0 || desc->N < 1 || desc->H < 1) return KMPC_ERR_INVALID;
     if (desc->H > KMPC_MV_MAX_H || desc->N * desc->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
-    if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
-    if (desc->allow_short) return KMPC_ERR_UNSUPPORTED;
-    if (max_weight >= 1.0)   // an inactive bound: the plain solve
+    double u;
+    const int rc = mv_box_limit(*desc, max_weight, u);
+    if (rc) return rc;
+    if (u == 0.0)   // an inactive bound: the plain solve
         return kmpc_solve_mv_ws(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
                                 ws_bytes, stream);
-    if (!((double)desc->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
     if (desc->B == 0) return KMPC_OK;
     if (!mu || !sigma || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
     return kmpc::mv_solve_launch(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
-                                 ws_bytes, (hipStream_t)stream, max_weight);
+                                 ws_bytes, (hipStream_t)stream, u);
 }
 
 int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int ldz,
@@ -365,13 +372,9 @@ int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc
     if (sweep && (n_cfg < 1 || (long long)n_cfg * bd->P > 0x7fffffffLL)) return KMPC_ERR_INVALID;
     if (d->H > KMPC_MV_MAX_H || (long long)d->N * d->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
     double u = 0.0;   // the active limit (0: the plain kernels)
-    if (max_weight != 0.0) {
-        if (!(max_weight > 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
-        if (d->allow_short) return KMPC_ERR_UNSUPPORTED;
-        if (max_weight < 1.0) {   // (>= 1: an inactive bound)
-            if (!((double)d->N * max_weight > 1.0)) return KMPC_ERR_INVALID;   // empty set or a single point
-            u = max_weight;
-        }
+    if (max_weight != 0.0) {   // (0: none, for these two entries only)
+        const int rc = mv_box_limit(*d, max_weight, u);
+        if (rc) return rc;
     }
     if (bd->P == 0 || n_steps == 0) return KMPC_OK;
     if (!mu || !sigma || !valid || !weights || !value || !hist || !target || !status || !obj ||

@@ -7,27 +7,21 @@
 namespace kmpc {
 
 // kmpc_solve.hip
-size_t solve_workspace_bytes(const kmpc_solve_desc* d);
-int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_prev, double* w_out,
-                 int* status, double* obj, int* iters, void* ws, size_t ws_bytes, hipStream_t stream,
-                 double* trace = nullptr);
-
-int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
-                     double* w_out, int* status, double* obj, int* iters, hipStream_t stream);
-// ... on the large-window box kernel (kmpc_solve_box_ws), and the workspace it needs
-size_t solve_bigbox_workspace_bytes(const kmpc_solve_desc* d);
-int solve_bigbox_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
-                        double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
-                        hipStream_t stream);
+// max_weight, here and below: the active per-asset position limit, validated by the caller (no short,
+// 1 / N < max_weight < 1), or 0.0 for none. The box family that runs d under a limit: the register
+// box kernels (no workspace), the large-window box kernel (solve_workspace_bytes), or none.
+enum class BoxFamily { NONE, REGISTER, LARGE };
+BoxFamily box_family(const kmpc_solve_desc* d, double max_weight);
+size_t solve_workspace_bytes(const kmpc_solve_desc* d, double max_weight);
+int solve_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                 double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
+                 hipStream_t stream, double* trace = nullptr);
 
 // the path-persistent backtest: the run (n_cfg = 0) or the sweep of n_cfg configs (BtLaunch:
-// kmpc_solve_args.h)
+// kmpc_solve_args.h); KMPC_ERR_UNSUPPORTED where the plan has no persistent kernel
 struct BtLaunch;
-int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const BtLaunch& l,
-                    double* target, int* status, double* obj, hipStream_t stream);
-// ... with the position limit max_weight in every step's solve (the box kernels)
-int backtest_box_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
-                        const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream);
+int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
+                    const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream);
 
 // kmpc_backtest.hip
 int gross_returns_launch(size_t n, const float* yhat, float* R, hipStream_t stream);

@@ -7,8 +7,11 @@
 //     per lane — for N <= 256 assets and H <= 10 periods, in the packed, mixed-precision C3,
 //     constant-case and generic forms; each horizon bound HM is instantiated in its own translation
 //     unit (kmpc_solve_h*.hip, kmpc_solve_p*.hip), the variant by the ladder of kmpc_solve_args.h.
-// kmpc_solve and its workspace query consume the plan; kmpc_backtest_run and kmpc_backtest_sweep
-// read from it whether a path-persistent kernel runs the body of the kernel kmpc_solve would pick.
+// A call with a per-asset position limit (kmpc_solve_box, kmpc_solve_box_ws) has two families of its
+// own: the box case of the generic ipm_kernel and the box form of ipm_big, at the same shape edges.
+// kmpc_solve, kmpc_solve_box(_ws) and their workspace queries consume the plan; kmpc_backtest_run and
+// kmpc_backtest_sweep and their box forms read from it whether a path-persistent kernel runs the
+// body of the kernel the solve would pick.
 #include <type_traits>
 
 #include "kmpc_internal.h"
@@ -28,7 +31,9 @@ namespace {
 // 78.88 / 78.69 — 2e-5 loses on random yhat; statuses as float64 at every threshold)
 constexpr double MU_HANDOFF = 3e-5;
 
-SolveArgs make_args(const kmpc_solve_desc* d) {
+// max_weight: the active per-asset position limit the caller (kmpc_capi.hip) has validated (no short,
+// 1 / N < max_weight < 1), or 0.0 for none — here and in every function below that takes it
+SolveArgs make_args(const kmpc_solve_desc* d, double max_weight) {
     SolveArgs a;
     a.B = d->B; a.N = d->N; a.H = d->H;
     a.c = d->cost_coeff;
@@ -42,6 +47,9 @@ SolveArgs make_args(const kmpc_solve_desc* d) {
     a.warm = nullptr;
     a.warm_floats = 0;
     a.mu_handoff = d->mu_handoff > 0.0 ? d->mu_handoff : MU_HANDOFF;
+    // (the limit shares mu_handoff's slot: the box kernels have no float32 phase, and the large-window
+    // kernel does not read the handoff)
+    if (max_weight > 0.0) a.max_weight = max_weight;
     return a;
 }
 
@@ -94,17 +102,35 @@ int by_horizon(int H, F&& f) {
     return KMPC_ERR_UNSUPPORTED;   // H > 10: the large-window kernel
 }
 
-enum class Family { SIMPLEX, LARGE, PACKED, MIXED_C3, CASE, GENERIC };
+// BOX, LARGE_BOX: the two families of a call with a position limit; NONE: no kernel runs it
+enum class Family { SIMPLEX, LARGE, PACKED, MIXED_C3, CASE, GENERIC, BOX, LARGE_BOX, NONE };
 struct Plan {
     Family family;
     // PACKED, CASE: the rung is the C3 one, and the path-persistent backtest kernels have a form of
-    // it (float64, case 7, H = HM: launch_bt_variant; one step's W0 only)
+    // it (float64, case 7, H = HM: launch_bt_variant; one step's W0 only). BOX: persistent past the
+    // packed shapes (N > 32: the box case has no packed form), at every H, one step's W0 only
+    // (launch_bt_box)
     bool c3 = false, persistent = false;
 };
 
-// The kernel family kmpc_solve runs a call on, for the precision asked (kmpc_solve_desc.precision)
-Plan solve_plan(const SolveArgs& a, int precision) {
+// The kernel family kmpc_solve runs a call on, for the precision asked (kmpc_solve_desc.precision),
+// and under a limit the family of kmpc_solve_box / kmpc_solve_box_ws
+Plan solve_plan(const SolveArgs& a, int precision, double max_weight) {
     Plan p{Family::GENERIC};
+    if (max_weight > 0.0) {
+        // One family per side at every batch size, float64 only: no presolve (the capped simplex has
+        // no closed form here), no packing, no mixed pair. The box case of the generic register
+        // kernels (launch_ipm_box, no workspace) where the register kernels run; elsewhere the box
+        // form of the large-window kernel (big_box_launch), which the register paths cannot ask for.
+        if (precision == KMPC_PRECISION_MIXED) return Plan{Family::NONE};
+        if (a.N <= 256 && a.H <= 10 && a.path != KMPC_PATH_LARGE) {
+            p.family = Family::BOX;
+            p.persistent = a.N > 32 && !a.return_full;
+            return p;
+        }
+        const bool reg = a.path == KMPC_PATH_REGISTER || a.path == KMPC_PATH_REGISTER_UNPACKED;
+        return Plan{reg ? Family::NONE : Family::LARGE_BOX};
+    }
     if (simplex_case(a)) return Plan{Family::SIMPLEX};
     if (use_big(a)) return Plan{Family::LARGE};
     const auto rung = [&](auto v) -> int {
@@ -159,8 +185,8 @@ int for_each_launch(const kmpc_solve_desc* d, const SolveIO& io, F&& launch) {
     return KMPC_OK;
 }
 
-SolveArgs make_args(const kmpc_solve_desc& d, const SolveIO& io) {
-    SolveArgs a = make_args(&d);
+SolveArgs make_args(const kmpc_solve_desc& d, double max_weight, const SolveIO& io) {
+    SolveArgs a = make_args(&d, max_weight);
     a.yhat = io.yhat; a.wp = io.w_prev; a.wout = io.w_out; a.status = io.status; a.obj = io.obj; a.iters = io.iters;
     a.trace = nullptr;
     return a;
@@ -200,70 +226,48 @@ int mixed_launch(const SolveArgs& a, void* ws, size_t ws_bytes, hipStream_t stre
 
 }  // namespace
 
-size_t solve_workspace_bytes(const kmpc_solve_desc* d) {
+BoxFamily box_family(const kmpc_solve_desc* d, double max_weight) {
+    switch (solve_plan(make_args(d, max_weight), d->precision, max_weight).family) {
+        case Family::BOX: return BoxFamily::REGISTER;
+        case Family::LARGE_BOX: return BoxFamily::LARGE;
+        default: return BoxFamily::NONE;
+    }
+}
+
+size_t solve_workspace_bytes(const kmpc_solve_desc* d, double max_weight) {
     if (!d || d->B <= 0) return 0;
-    const SolveArgs a = make_args(d);
-    switch (solve_plan(a, d->precision).family) {
+    const SolveArgs a = make_args(d, max_weight);
+    switch (solve_plan(a, d->precision, max_weight).family) {
         case Family::LARGE: return big_ws_bytes(a);
+        case Family::LARGE_BOX: return big_box_ws_bytes(a);   // two more slab arrays
         case Family::MIXED_C3: return warm_bytes(a);
         default: return 0;
     }
 }
 
-int solve_launch(const kmpc_solve_desc* d, const float* yhat, const double* w_prev, double* w_out,
-                 int* status, double* obj, int* iters, void* ws, size_t ws_bytes, hipStream_t stream,
-                 double* trace) {
+int solve_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
+                 double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
+                 hipStream_t stream, double* trace) {
     const SolveIO io = {yhat, w_prev, w_out, status, obj, iters};
     return for_each_launch(d, io, [&](const kmpc_solve_desc& c, const SolveIO& s, bool first) -> int {
-        SolveArgs a = make_args(c, s);
+        SolveArgs a = make_args(c, max_weight, s);
         a.trace = first ? trace : nullptr;
         if (a.B == 0) return KMPC_OK;
-        switch (solve_plan(a, c.precision).family) {
+        switch (solve_plan(a, c.precision, max_weight).family) {
             case Family::SIMPLEX: return simplex_launch(a, stream);
             case Family::LARGE: return big_launch(a, ws, ws_bytes, stream);
             case Family::PACKED:
                 return by_horizon(a.H, [&](auto hm) { return launch_ipm_packed<decltype(hm)::value>(a, stream); });
             case Family::MIXED_C3: return mixed_launch(a, ws, ws_bytes, stream);
             case Family::CASE: return a.H == 10 ? launch_ipm_case<10>(a, stream) : launch_ipm_case<5>(a, stream);
+            case Family::BOX:
+                return by_horizon(a.H, [&](auto hm) { return launch_ipm_box<decltype(hm)::value>(a, stream); });
+            // (one launch per LAUNCH_MAX_B windows over the same slabs: the launches are ordered on the stream)
+            case Family::LARGE_BOX: return big_box_launch(a, ws, ws_bytes, stream);
+            case Family::NONE: return KMPC_ERR_UNSUPPORTED;
             case Family::GENERIC: break;
         }
         return by_horizon(a.H, [&](auto hm) { return launch_ipm<decltype(hm)::value>(a, stream); });
-    });
-}
-
-// kmpc_solve_box: the program of kmpc_solve with a per-asset position limit w <= max_weight, in the
-// box case of the generic float64 register kernels (launch_ipm_box) at every batch size: no
-// presolve (the capped simplex has no closed form here), no packing, no mixed pair, no workspace.
-// The caller (kmpc_capi.hip) has checked the shape and the limit: no short, 1 / N < max_weight < 1,
-// N <= 256, H <= 10.
-int solve_box_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
-                     double* w_out, int* status, double* obj, int* iters, hipStream_t stream) {
-    const SolveIO io = {yhat, w_prev, w_out, status, obj, iters};
-    return for_each_launch(d, io, [&](const kmpc_solve_desc& c, const SolveIO& s, bool) -> int {
-        SolveArgs a = make_args(c, s);
-        a.max_weight = max_weight;   // (shares mu_handoff's slot: the box kernels have no float32 phase)
-        if (a.B == 0) return KMPC_OK;
-        return by_horizon(a.H, [&](auto hm) { return launch_ipm_box<decltype(hm)::value>(a, stream); });
-    });
-}
-
-// kmpc_solve_box_ws past the register box kernels (N > 256, H > 10 or KMPC_PATH_LARGE): the box form
-// of the large-window kernel, one launch per LAUNCH_MAX_B windows over the same slabs (the launches
-// are ordered on the stream). The caller has checked the shape and the limit as for solve_box_launch.
-size_t solve_bigbox_workspace_bytes(const kmpc_solve_desc* d) {
-    if (!d || d->B <= 0) return 0;
-    return big_box_ws_bytes(make_args(d));
-}
-
-int solve_bigbox_launch(const kmpc_solve_desc* d, double max_weight, const float* yhat, const double* w_prev,
-                        double* w_out, int* status, double* obj, int* iters, void* ws, size_t ws_bytes,
-                        hipStream_t stream) {
-    const SolveIO io = {yhat, w_prev, w_out, status, obj, iters};
-    return for_each_launch(d, io, [&](const kmpc_solve_desc& c, const SolveIO& s, bool) -> int {
-        SolveArgs a = make_args(c, s);
-        a.max_weight = max_weight;   // (shares mu_handoff's slot, which the large-window kernel does not read)
-        if (a.B == 0) return KMPC_OK;
-        return big_box_launch(a, ws, ws_bytes, stream);
     });
 }
 
@@ -277,41 +281,30 @@ int solve_bigbox_launch(const kmpc_solve_desc* d, double max_weight, const float
 // max_turnover. The sweep's parameters are device arrays, so the constraint case cannot depend on
 // them: always the constant case 7 (the caller has set sd's cost_coeff and max_turnover to it) in
 // float64 — no mixed pair at any batch size, and none to ask for.
-int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, int n_cfg, const BtLaunch& l,
-                    double* target, int* status, double* obj, hipStream_t stream) {
+// With a position limit (kmpc_backtest_run_box, kmpc_backtest_sweep_box) every step's solve is
+// kmpc_solve_box's, the window body that of the box kernel it runs for the shape (launch_bt_box);
+// the sweep's constraint case is read at run time there (the generic kernel).
+int backtest_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
+                    const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream) {
     const bool sweep = n_cfg > 0;
-    SolveArgs a = make_args(sd);
+    SolveArgs a = make_args(sd, max_weight);
     if (sweep && sd->precision == KMPC_PRECISION_MIXED) return KMPC_ERR_UNSUPPORTED;
-    // (the kernel kmpc_solve picks for this batch)
-    const Plan p = solve_plan(a, sweep ? KMPC_PRECISION_F64 : sd->precision);
+    // (the kernel kmpc_solve, or under a limit kmpc_solve_box, picks for this batch)
+    const Plan p = solve_plan(a, sweep ? KMPC_PRECISION_F64 : sd->precision, max_weight);
     if (!p.persistent) return KMPC_ERR_UNSUPPORTED;
     if (bd->P == 0 || l.n_steps == 0) return KMPC_OK;
     a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
     a.yhat = l.yhat; a.wp = l.weights;
     const auto run = [&](auto sw) {
         constexpr bool SW = decltype(sw)::value;
+        if (p.family == Family::BOX)
+            return by_horizon(a.H, [&](auto hm) { return launch_bt_box<decltype(hm)::value, SW>(a, l, stream); });
         if (p.family == Family::PACKED)
             return by_horizon(a.H, [&](auto hm) { return launch_bt_packed<decltype(hm)::value, SW>(a, l, stream); });
         if (p.c3) return launch_bt_c3<SW>(a, l, stream);
         return a.H == 5 ? launch_bt_case<5, SW>(a, l, stream) : launch_bt_case<10, SW>(a, l, stream);
     };
     return sweep ? run(std::true_type{}) : run(std::false_type{});
-}
-
-// kmpc_backtest_run_box (n_cfg = 0) and kmpc_backtest_sweep_box: the same launch with the per-asset
-// position limit w <= max_weight in every step's solve, the window body that of the box kernel
-// kmpc_solve_box runs for the shape (launch_bt_box). No plan: the box solve is one kernel family at
-// every batch size. The caller (kmpc_capi.hip) has checked the shape and the limit: no short,
-// 1 / N < max_weight < 1, 32 < N <= 256, H <= 10, float64, W0 only.
-int backtest_box_launch(const kmpc_backtest_desc* bd, const kmpc_solve_desc* sd, double max_weight, int n_cfg,
-                        const BtLaunch& l, double* target, int* status, double* obj, hipStream_t stream) {
-    if (bd->P == 0 || l.n_steps == 0) return KMPC_OK;
-    SolveArgs a = make_args(sd);
-    a.max_weight = max_weight;   // (shares mu_handoff's slot: the box kernels have no float32 phase)
-    a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr; a.trace = nullptr;
-    a.yhat = l.yhat; a.wp = l.weights;
-    if (n_cfg > 0) return by_horizon(a.H, [&](auto hm) { return launch_bt_box<decltype(hm)::value, true>(a, l, stream); });
-    return by_horizon(a.H, [&](auto hm) { return launch_bt_box<decltype(hm)::value, false>(a, l, stream); });
 }
 
 }  // namespace kmpc

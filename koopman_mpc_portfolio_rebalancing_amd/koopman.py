@@ -283,8 +283,8 @@ class DeviceKoopman:
         B = x.shape[0]
         H = int(mpc_config.horizon)
         if _box_limit(mpc_config, n_assets):
-            # a position limit (MPCConfig.max_weight): kmpc_solve_desc cannot carry it, so no fused
-            # kmpc_window — kmpc_rollout, then kmpc_solve_box on the same stream
+            # a position limit (MPCConfig.max_weight, mpc._box_limit): no fused kmpc_window —
+            # kmpc_rollout, then kmpc_solve_box on the same stream
             if w_prev.shape != (B, int(n_assets)):
                 raise ValueError(f"w_prev must be [{B}, {int(n_assets)}], got {tuple(w_prev.shape)}")
             with torch.cuda.device(self.device):

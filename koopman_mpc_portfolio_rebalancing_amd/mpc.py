@@ -139,28 +139,24 @@ def solve_mpc_log_utility_batched(
     d = _solve_desc(B, N, H, config, return_full)
     L = _lib.load()
     u = _box_limit(config, N)
-    if u and _box_route(d) == "large":   # the large-window box kernel (its slabs: a workspace)
-        with torch.cuda.device(y.device):
-            nws = int(L.kmpc_solve_box_workspace_bytes(ctypes.byref(d), u))
-            ws = _workspace(y.device, nws)
-            rc = L.kmpc_solve_box_ws(ctypes.byref(d), u, y.data_ptr(), wp.data_ptr(), W.data_ptr(),
-                                     status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                                     ws.data_ptr(), nws, _lib.stream_handle(y.device))
-        _lib.check(rc)
-        return (W, status, value, iters) if with_iters else (W, status, value)
-    if u:   # the position limit: the box case of the float64 register kernels (no workspace)
-        with torch.cuda.device(y.device):
-            rc = L.kmpc_solve_box(ctypes.byref(d), u, y.data_ptr(), wp.data_ptr(), W.data_ptr(),
-                                  status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                                  _lib.stream_handle(y.device))
-        _lib.check(rc)
-        return (W, status, value, iters) if with_iters else (W, status, value)
+    # The entry, its arguments ahead of the arrays and its workspace query: kmpc_solve; under a limit
+    # kmpc_solve_box (the box case of the float64 register kernels: no workspace argument) or
+    # kmpc_solve_box_ws (the large-window box kernel, its slabs in a workspace)
+    arrays = (y.data_ptr(), wp.data_ptr(), W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr())
+    if not u:
+        entry, head, query = L.kmpc_solve, (ctypes.byref(d),), lambda: L.kmpc_workspace_bytes(None, ctypes.byref(d))
+    elif _box_route(d) == "large":
+        entry, head = L.kmpc_solve_box_ws, (ctypes.byref(d), u)
+        query = lambda: L.kmpc_solve_box_workspace_bytes(ctypes.byref(d), u)
+    else:
+        entry, head, query = L.kmpc_solve_box, (ctypes.byref(d), u), None
     with torch.cuda.device(y.device):
-        nws = int(L.kmpc_workspace_bytes(None, ctypes.byref(d)))
-        ws = _workspace(y.device, nws) if nws else None
-        rc = L.kmpc_solve(ctypes.byref(d), y.data_ptr(), wp.data_ptr(), W.data_ptr(),
-                          status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                          ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(y.device))
+        tail = ()
+        if query is not None:
+            nws = int(query())
+            ws = _workspace(y.device, nws) if nws or u else None   # (kmpc_solve_box_ws: never a null workspace)
+            tail = (ws.data_ptr() if ws is not None else None, nws)
+        rc = entry(*head, *arrays, *tail, _lib.stream_handle(y.device))
     _lib.check(rc)
     if with_iters:
         return W, status, value, iters
@@ -289,14 +285,11 @@ def solve_mpc_mean_variance_batched(
     with torch.cuda.device(dev):
         nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(d)))
         ws = _workspace(dev, nws) if nws else None
-        if u:   # the position limit: the BOX form of the same kernels, same workspace
-            rc = L.kmpc_solve_mv_box(ctypes.byref(d), u, mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
-                                     W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                                     ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
-        else:
-            rc = L.kmpc_solve_mv_ws(ctypes.byref(d), mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
-                                    W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
-                                    ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
+        # (the position limit: the BOX form of the same kernels, same workspace)
+        entry, head = (L.kmpc_solve_mv_box, (ctypes.byref(d), u)) if u else (L.kmpc_solve_mv_ws, (ctypes.byref(d),))
+        rc = entry(*head, mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
+                   W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                   ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
     _lib.check(rc)
     if with_iters:
         return W, status, value, iters

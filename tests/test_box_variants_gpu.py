@@ -11,7 +11,7 @@ registers: kernel_of below). Each is run here
 * and, for a register-cold, a shared-slot and an all-LDS kernel, against closed forms, at the edges
   of the limit and of w_prev, and with extreme forecasts;
 
-and the launch split of solve_box_launch past 2^22 windows. The bars are the project's (DESIGN
+and the launch split of kmpc_solve_box past 2^22 windows. The bars are the project's (DESIGN
 §Parity): objective 1e-6 + 1e-5 |f|, W[0] 1e-3, budget and turnover 1e-8, bounds 1e-9 (box_ref.violated),
 value == reference_objective(W) to 1e-12. The input conditions a case relies on are asserted on the
 inputs; no window is left out of an assertion otherwise.
@@ -387,7 +387,7 @@ def test_tiny_gross_return_period_is_solved(N, H):
 # ---- the launch split ---------------------------------------------------------------------------
 
 def test_box_launch_split_past_4m_windows():
-    """Past 2^22 windows solve_box_launch goes as equal launches, each at its own offset into yhat,
+    """Past 2^22 windows kmpc_solve_box goes as equal launches, each at its own offset into yhat,
     w_prev, the [B, H, N] output (return_full), status, value and iterations: 2^22 + 64 windows at
     N = 3, H = 2 (tau = 0: no window is infeasible), generated on the device — every window optimal,
     and the 4,096 windows around the split equal the same windows solved alone, bit for bit."""
