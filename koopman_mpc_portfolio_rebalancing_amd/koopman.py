@@ -59,14 +59,6 @@ class KoopmanModelSpec:
     lista_thresh: float = 0.0
 
     @property
-    def fuse_latent(self) -> bool:
-        return self.latent_form != "unfused"
-
-    @fuse_latent.setter
-    def fuse_latent(self, v: bool) -> None:
-        self.latent_form = "auto" if v else "unfused"
-
-    @property
     def latent(self) -> int:
         return int(self.kmat.shape[0])
 
