@@ -264,7 +264,7 @@ typedef struct kmpc_rollout_desc {
                                  epilogues; BASELINE configs[4]) or KMPC_DTYPE_F32_F32MFMA (2)   */
     int latent_unfused;       /* the H-step latent loop (KMPC_LATENT_*, same fp32 arithmetic up to
                                  summation order; A/B and tests):
-                                 0 AUTO: the library's choice — from KMPC_LATPOW_MINB (8,192) windows
+                                 0 AUTO: the library's choice — from 8,192 windows (LATPOW_MINB)
                                    with a linear latent step (norm 'id', LISTA) one GEMM of z_0 against
                                    the latent powers D_N (K^T)^t, else one fused launch;
                                  1 UNFUSED: one GEMM launch per step;

@@ -4,7 +4,7 @@ every kernel, epilogue, threshold side and edge shape; the mirror below is pinne
 constants; reference and bound hold on CPU restatements) and test_rollout_variants_gpu.py (every cell
 on the device against float64).
 
-plan() is a hand mirror of gemm() and rollout_launch(): the ordered launches of one rollout as
+plan() is a hand mirror of route_gemm() and plan_rollout(): the ordered launches of one rollout as
 (kernel, epilogue, M, N, K). Kernel names:
 
 * fp32 GEMMs on three bf16 planes, x3_split64 / x3_mid44 / x3_big42 (gemm_nt_x3_kernel: the 64-square
@@ -34,13 +34,13 @@ K_MAX_CAP, K_RMS_CAP = 32.0, 2.0     # fixed: inputs whose CPU restatements need
 X3_EXTRA = 3.0                        # three planes drop at most 2.01 u |a b| per product (derived)
 PLANE_VS_F32 = 1.5                    # plane kernels: rms within 1.5 x the f32-input kernel's
 
-# ---- the library's constants (pinned to kmpc_rollout.hip by test_rollout_variants_cpu.py) ---------
-LAT16_MAXB = 8192        # KMPC_LAT16_MAXB: batches below run the 16-row loop
-LATPOW_MINB = 8192       # KMPC_LATPOW_MINB: the latent-powers GEMM from here ('auto')
-LAT16_WAVES = 8          # KMPC_LAT16_WAVES: the 16-row loop at any batch while L <= 16 * this
-F32_SPLITK = 4           # KMPC_F32_SPLITK: slices of the fp32 split, taken from K >= 128 * this
-GEMM_MID, GEMM_BIG = 44, 42
-BF16_SPLIT_MINK = 2048   # KMPC_BF16_SPLIT_MINK
+# ---- the library's constants (pinned to kmpc_rollout.hip's by test_rollout_variants_cpu.py) -------
+LAT16_MAXB = 8192        # batches below run the 16-row loop
+LATPOW_MINB = 8192       # the latent-powers GEMM from here ('auto')
+LAT16_WAVES = 8          # the 16-row loop at any batch while L <= 16 * this
+F32_SPLITK = 4           # slices of the fp32 split, taken from K >= 128 * this
+GEMM_MID, GEMM_BIG = 44, 42     # TILE_128_44 below BIG_TILES, TILE_128_42 from there
+BF16_SPLIT_MINK = 2048   # K from which bf16 splits
 BF16_SPLIT = 8           # SPLITK_BUF: slices of the bf16 split
 SPLITK_ELEMS = 256 * 64 * 64
 BIG_TILES = 512          # 128-square tiles from which the large form runs
@@ -70,7 +70,7 @@ def _ceil(a, b):
 
 
 def gemm(M, N, K, epi, dtype, raw_ok=False):
-    """gemm() of kmpc_rollout.hip: the launches of one GEMM with a fused epilogue."""
+    """route_gemm() of kmpc_rollout.hip: the launches of one GEMM with a fused epilogue."""
     if M <= 0 or N <= 0:
         return []
     t128 = _ceil(N, 128) * _ceil(M, 128)
@@ -95,7 +95,7 @@ def fusable(L, kind, norm, dtype, form, n_dec_layers):
 
 def plan_stages(B, obs, enc_dims, L, N, H, kind="generic", norm="id", dtype="fp32", form="auto", n_dec_layers=1,
                 lista_loops=0, panel=False, enc_act="relu", enc_last_relu=False, dec_act="relu", dec_hidden=None):
-    """rollout_launch(): [(stage, (kernel, epilogue, M, N, K))]. enc_dims are the encoder's layer widths
+    """plan_rollout() and rollout_launch(): [(stage, (kernel, epilogue, M, N, K))]. enc_dims are the encoder's layer widths
     after obs (the last is L); panel changes the first layer's row stride only, not its launch."""
     assert enc_dims[-1] == L and N <= obs
     ball = kind == "generic" and norm == "ball"

@@ -375,6 +375,60 @@ def test_fused_z0_is_never_read():
     assert torch.equal(outs[0], km.rollout(x, m, s, H, N))
 
 
+# (id, kind, B, obs, L, N, H, dtype, latent form, LISTA loops, the kernel the shape is there for)
+WS_CASES = [("bf16_split8", "generic", 200, 2048, 100, 33, 2, "bf16", "auto", 0, "bf16_split8"),
+            ("planes", "generic", 8257, 132, 256, 33, 2, "fp32", "sequential", 0, "latx3"),
+            ("powers", "generic", 8192, 132, 128, 33, 3, "fp32", "auto", 0, "powers"),
+            ("lista", "lista", 300, 132, 64, 33, 2, "fp32", "auto", 2, "shrink")]
+
+
+@pytest.mark.parametrize("case", WS_CASES, ids=[c[0] for c in WS_CASES])
+def test_rollout_stays_inside_its_workspace(case):
+    """kmpc_rollout with exactly kmpc_workspace_bytes of a buffer that is 4,096 bytes longer and filled
+    with 0xA5: the trailing bytes stay untouched and yhat is bit for bit that of DeviceKoopman.rollout.
+    The untouched tail is the check of the layout's far end; the equality only says that the call made
+    by hand is the call the package makes (both go through the same layout, so an overlap of two
+    regions inside the workspace is for the reference tests of this file to find, not for this one).
+    The shapes reach the far end of the regions whose sizes are not a plain [rows, width]: the eight
+    bf16 split-K slices (the encoder GEMM 200 x 100 x 2,048), the bf16 plane block (latent_steps_x3_kernel,
+    N = 33 padded to 64 decoder rows), the powers block with the tiled epilogue at the workspace's very
+    end, and the LISTA path (S^T, c in z1, two loops through ping). The mirror's plan() says that each
+    shape takes the route it is there for."""
+    import ctypes
+    import rollout_variants as rv
+    from koopman_mpc_portfolio_rebalancing_amd import _lib
+    _, kind, B, obs, L, N, H, dtype, form, loops, kernel = case
+    stages = rv.plan_stages(B, obs, [L], L, N, H, kind=kind, dtype=dtype, form=form, lista_loops=loops)
+    kernels = [g[0] for _, g in stages]
+    assert kernel in kernels, kernels
+    if kernel == "bf16_split8":
+        assert stages[:2] == [("enc0", ("bf16_split8", "parts", B, L, obs)), ("enc0", ("splitk_epi", "none", B, L, obs))]
+    elif kernel == "shrink":
+        assert [s for s, _ in stages if s.startswith("lista")] == ["lista0", "lista1"]
+    else:
+        assert kernels[-1] == {"latx3": "latx3", "powers": "x3_mid44"}[kernel]
+    dev = torch.device("cuda")
+    gen = torch.Generator().manual_seed(11)
+    rnd = lambda r, c: torch.randn(r, c, generator=gen) / np.sqrt(c)   # noqa: E731
+    spec = KoopmanModelSpec(kind=kind, encoder=[(rnd(L, obs), None if kind == "lista" else 0.1 * rnd(1, L)[0])],
+                            kmat=rnd(L, L), decoder=[(rnd(obs, L), None)],
+                            lista_S=0.5 * rnd(L, L) if kind == "lista" else None, lista_loops=loops,
+                            lista_thresh=0.01 if kind == "lista" else 0.0)
+    km = DeviceKoopman(spec, dev, dtype=dtype, latent_form=form)
+    x = torch.randn(B, obs, generator=gen).to(dev)
+    m = torch.linspace(-1e-3, 1e-3, N, device=dev)
+    s = torch.linspace(0.01, 0.02, N, device=dev)
+    d = km.rollout_desc(B, H, N, m, s)
+    Lb = _lib.load()
+    nbytes = Lb.kmpc_workspace_bytes(ctypes.byref(d), None)
+    ws = torch.full((nbytes + 4096,), 0xA5, dtype=torch.uint8, device=dev)
+    y = torch.empty((B, H, N), dtype=torch.float32, device=dev)
+    _lib.check(Lb.kmpc_rollout(ctypes.byref(d), x.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_handle(dev)))
+    assert bool((ws[nbytes:] == 0xA5).all())
+    assert torch.isfinite(y).all()
+    assert torch.equal(y, km.rollout(x, m, s, H, N))
+
+
 def _ref64(sd, x, H, N, mean, std):
     """GenericKM (relu encoder, norm id, one-layer decoder) in float64 (torch CPU, double)."""
     h = x.double()

@@ -14,37 +14,68 @@ from koopman_mpc_portfolio_rebalancing_amd import DeviceKoopman, KoopmanModelSpe
 from oracle import rollout as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "koopman_mpc_portfolio_rebalancing_amd", "csrc", "kmpc_rollout.hip")).read()
+CSRC = os.path.join(ROOT, "koopman_mpc_portfolio_rebalancing_amd", "csrc")
+SRC = "".join(open(os.path.join(CSRC, f)).read() for f in ("kmpc_rollout_gemm.h", "kmpc_rollout_latent.h", "kmpc_rollout.hip"))
+# the compile-time switches the rollout once had: the first row's were pinned to "on" (KMPC_F32_GEMM to
+# the three-plane form) and are gone with their other side, the second row's values are constexpr now
+REMOVED = ("KMPC_LATPOW", "KMPC_LATX3", "KMPC_Z0_FUSE", "KMPC_BF16_SPLITK", "KMPC_BF16_SMALL", "KMPC_F32_GEMM",
+           "KMPC_GEMM_MID", "KMPC_GEMM_BIG", "KMPC_GEMM_BK1", "KMPC_X3_TIMING", "KMPC_X3_DB", "KMPC_LAT_WAVES",
+           "KMPC_LAT16_MAXB", "KMPC_LATPOW_MINB", "KMPC_LAT16_WAVES", "KMPC_F32_SPLITK", "KMPC_BF16_SPLIT_MINK")
 
 
-def _define(name):
-    """The default of '#define NAME value' (a product of integers) in kmpc_rollout.hip."""
-    m = re.search(r"#define %s \(?([0-9* ]+?)\)?\s*$" % name, SRC, re.M)
-    return int(np.prod([int(t) for t in m.group(1).split("*")]))
+def _const(name):
+    """The value of 'constexpr int NAME = value;' (a product of integers; size_t too), defined once in the
+    rollout's three files."""
+    m = re.findall(r"^constexpr (?:int|size_t) %s = (?:\(size_t\))?([0-9* ]+);" % name, SRC, re.M)
+    assert len(m) == 1, (name, m)
+    return int(np.prod([int(t) for t in m[0].split("*")]))
 
 
 def test_mirror_constants_equal_the_librarys():
-    assert rv.LAT16_MAXB == _define("KMPC_LAT16_MAXB")
-    assert rv.LATPOW_MINB == _define("KMPC_LATPOW_MINB")
-    assert rv.LAT16_WAVES == _define("KMPC_LAT16_WAVES")
-    assert rv.F32_SPLITK == _define("KMPC_F32_SPLITK")
-    assert rv.GEMM_MID == _define("KMPC_GEMM_MID") and rv.GEMM_BIG == _define("KMPC_GEMM_BIG")
-    assert rv.BF16_SPLIT_MINK == _define("KMPC_BF16_SPLIT_MINK")
-    assert all(_define(n) == 1 for n in ("KMPC_LATPOW", "KMPC_LATX3", "KMPC_Z0_FUSE", "KMPC_BF16_SPLITK", "KMPC_BF16_SMALL"))
-    assert _define("KMPC_F32_GEMM") == 2                       # dtype fp32 is the three-plane form
-    m = re.search(r"SPLITK_ELEMS = \(size_t\)(\d+) \* (\d+) \* (\d+);", SRC)
-    assert rv.SPLITK_ELEMS == int(m.group(1)) * int(m.group(2)) * int(m.group(3))
-    assert rv.BF16_SPLIT == int(re.search(r"constexpr int SPLITK_BUF = (\d+);", SRC).group(1))
-    # the tile-count thresholds of gemm() and the K bound of the fp32 split
-    assert rv.BIG_TILES == int(re.search(r"\} else if \(\(size_t\)grid\.x \* grid\.y < (\d+)\) \{", SRC).group(1))
-    assert rv.SPLIT_TILES64 == int(re.search(r"\(size_t\)grid64\.x \* grid64\.y < (\d+) && g\.K >= 128 \* SPLITK\)", SRC).group(1))
-    assert rv.BF16_FEW == int(re.search(r"const bool few = \(size_t\)grid\.x \* grid\.y < (\d+);", SRC).group(1))
-    # latent_fusable, the 16-row loop's reach and the three-plane loop's latent
-    m = re.search(r"d->L % (\d+) == 0 &&\s+d->L <= (\d+)", SRC)
-    assert (rv.FUSE_L_MULT, rv.FUSE_L_MAX) == (int(m.group(1)), int(m.group(2)))
-    assert "(Bn < KMPC_LAT16_MAXB || L <= 16 * KMPC_LAT16_WAVES)" in SRC
-    assert re.search(r"bf == 2 && !la\.ball && L == (\d+)\)", SRC).group(1) == str(rv.LATX3_L)
-    assert "Bn >= KMPC_LATPOW_MINB" in SRC
+    assert rv.LAT16_MAXB == _const("LAT16_MAXB")
+    assert rv.LATPOW_MINB == _const("LATPOW_MINB")
+    assert rv.LAT16_WAVES == _const("LAT16_WAVES")
+    assert rv.F32_SPLITK == _const("F32_SPLITK")
+    assert rv.BF16_SPLIT_MINK == _const("BF16_SPLIT_MINK")
+    assert rv.SPLITK_ELEMS == _const("SPLITK_ELEMS")
+    assert rv.BF16_SPLIT == _const("SPLITK_BUF")
+    # no switch is left: the names are gone, and nothing in the three files can be set from the command line
+    for name in REMOVED:
+        assert not re.search(r"\b%s\b" % name, SRC), name
+    assert not re.search(r"#\s*(define|ifndef|ifdef|if)\b", SRC)
+    # dtype fp32 is the three-plane form, fp32_f32mfma the run-time selector of the other
+    assert "g.bf16 = r.dtype == KMPC_DTYPE_F32 ? 2 : r.dtype == KMPC_DTYPE_BF16 ? 1 : 0;" in SRC
+    assert re.search(r"if \(g\.bf16 == 2\)\s+hipLaunchKernelGGL\(\(gemm_nt_x3_kernel<", SRC)
+    # the tile-count thresholds of route_gemm() and the K bound of the fp32 split
+    assert rv.BIG_TILES == _const("BIG_TILES")
+    assert rv.SPLIT_TILES64 == _const("SPLIT_TILES64")
+    assert rv.BF16_FEW == _const("BF16_FEW")
+    assert "const size_t t128 = (size_t)((N + 127) / 128) * ((M + 127) / 128);" in SRC
+    assert "const size_t t64 = (size_t)((N + 63) / 64) * ((M + 63) / 64);" in SRC
+    assert "const bool few = t128 < BF16_FEW;" in SRC
+    assert "if (few && have_part && K >= BF16_SPLIT_MINK && (size_t)M * N <= SPLITK_ELEMS)" in SRC
+    assert "return {dtype, TILE_128, SPLITK_BUF, TAIL_EPILOGUE};" in SRC
+    assert "return {dtype, few ? TILE_64 : TILE_128, 1, TAIL_NONE};" in SRC          # (the 64-square tile is on)
+    assert "if (have_part && t64 < SPLIT_TILES64 && K >= 128 * F32_SPLITK)" in SRC
+    # the two forms of the ladder: 16 waves of 32 x 32 below BIG_TILES, 8 waves of 32 x 64 from there
+    m = re.search(r"if \(t128 < BIG_TILES\) \{\n(?:.*\n){2}\s+return \{dtype, TILE_128_(\d+), 1, TAIL_NONE\};\n    \}\n"
+                  r"    return \{dtype, TILE_128_(\d+), 1, TAIL_NONE\};", SRC)
+    assert (rv.GEMM_MID, rv.GEMM_BIG) == (int(m.group(1)), int(m.group(2)))
+    assert re.search(r"r\.tile == TILE_64\) \{\s+launch_f32<1, 1, 2, 2>\(", SRC)
+    assert re.search(r"r\.tile == TILE_128_44\) \{\s+launch_f32<1, 1, 4, 4>\(", SRC)
+    assert re.search(r"\} else \{\s+launch_f32<1, 2, 4, 2>\(", SRC)
+    # latent_fusable, the 16-row loop's reach, the three-plane loop's latent, the powers, and z0 as partials
+    assert (rv.FUSE_L_MULT, rv.FUSE_L_MAX) == (_const("FUSE_L_MULT"), _const("FUSE_L_MAX"))
+    assert "d->L % FUSE_L_MULT == 0 && d->L <= FUSE_L_MAX" in SRC
+    assert "const bool lat16 = fus && (B < LAT16_MAXB || L <= 16 * LAT16_WAVES);" in SRC
+    assert "const bool kdir = lat16 && B < LAT16_MAXB;" in SRC
+    assert rv.LATX3_L == _const("LATX3_L")
+    assert ": d->dtype == KMPC_DTYPE_F32 && !p.ball && L == LATX3_L ? LOOP_LATX3 : LOOP_LAT32;" in SRC
+    assert "latent_steps_x3_kernel<8, LATX3_L>" in SRC
+    assert ("const bool latpow = d->latent_unfused == KMPC_LATENT_AUTO && fus && B >= LATPOW_MINB && !p.ball;"
+            in SRC)                                                                   # (the powers are on)
+    assert "p.loop = latpow ? LOOP_POWERS : !fus ? LOOP_STEPS : lat16 ? (kdir ? LOOP_LAT16_KDIR : LOOP_LAT16_KT)" in SRC
+    assert "p.zfuse = p.fused && d->model_kind == KMPC_MODEL_GENERIC && !p.ball;" in SRC   # (z0 as partials is on)
 
 
 def _probes():
