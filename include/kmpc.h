@@ -460,6 +460,35 @@ int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double*
                       size_t sigma_stride, const double* w_prev, double* w_out, int* status, double* obj,
                       int* iters, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- mean-variance MPC with an L1 turnover cap (added within ABI 0.7.0, see the version note at
+ * the end): the program of kmpc_solve_mv_ws (of kmpc_solve_mv_box where max_weight is given) with one
+ * more constraint per period, sum_i |w_t,i - w_{t-1},i| <= max_turnover (w_{-1} = w_prev), with or
+ * without allow_short. Arrays, statuses and the fallback are those of kmpc_solve_mv_ws. The cap is one
+ * more inequality per period on the epigraph rows s >= |d| (kept at cost_coeff = 0 too) inside the
+ * same interior point: slack and multiplier per period, the same Cholesky, a 2H x 2H Schur system.
+ * Unlike the uncapped programs this one can be infeasible: period 0 needs d0 <= max_turnover, d0 the
+ * L1 distance from w_prev to the feasible set — the mass of w_prev outside its bounds (below 0 when
+ * long-only, above max_weight under a limit) plus the budget gap |1 - sum clip(w_prev)| of the clipped
+ * vector; with allow_short just |1 - sum w_prev|. d0 > max_turnover reports KMPC_STATUS_INFEASIBLE
+ * for that window, before any iteration, with the fallback (tile(w_prev), obj NaN); the other windows
+ * are not affected. A w_prev on the simplex under no limit has d0 = 0.
+ * The workspace is kmpc_mv_cap_workspace_bytes(desc): the CAP kernels' slab per window in flight
+ * (n (n + 1) / 2 + 2 H n doubles, n = H*N), 0 up to H*N = 128. kmpc_mv_workspace_bytes is too small.
+ * Return codes, all decided before any launch (and before the B == 0 return), in this order:
+ *   - desc is checked as for kmpc_solve_mv_ws;
+ *   - max_turnover NaN or < 0: KMPC_ERR_INVALID;
+ *   - max_turnover == 0 (no cap): the call IS kmpc_solve_mv_ws (max_weight == 0) or
+ *     kmpc_solve_mv_box (otherwise) with the same arguments, their rules and workspace, bit-identical
+ *     results;
+ *   - max_weight == 0: no position limit (and allow_short is allowed); otherwise the rules of
+ *     kmpc_solve_mv_box in its order (NaN or < 0 KMPC_ERR_INVALID, allow_short KMPC_ERR_UNSUPPORTED,
+ *     >= 1 an inactive bound, N * max_weight <= 1 KMPC_ERR_INVALID);
+ *   - then KMPC_ERR_WORKSPACE past H*N = 128 without kmpc_mv_cap_workspace_bytes(desc) bytes. */
+size_t kmpc_mv_cap_workspace_bytes(const kmpc_mv_desc* desc);
+int kmpc_solve_mv_cap(const kmpc_mv_desc* desc, double max_weight, double max_turnover, const double* mu,
+                      const double* sigma, size_t sigma_stride, const double* w_prev, double* w_out, int* status,
+                      double* obj, int* iters, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- Markowitz rolling moments: MarkowitzStrategy.rebalance (baselines.py:70-88) ------------ */
 /* For window b at test row t = ts[b]: returns r_s = z_s * std + mean (float32, as
  * destandardize_returns, data_finance.py:740-742) of the standardized rows z [T, ldz] (first N
@@ -526,6 +555,33 @@ int kmpc_markowitz_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mv
                          double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
                          void* stream);
 
+/* kmpc_markowitz_run / kmpc_markowitz_sweep under the turnover cap of kmpc_solve_mv_cap (added within
+ * ABI 0.7.0): every valid step's window is kmpc_solve_mv_cap's, from the path's current (drifted)
+ * weights; a step whose window is infeasible (under a limit, weights drifted above it by more than the
+ * cap allows back: d0 > max_turnover) reports KMPC_STATUS_INFEASIBLE, holds, and the path goes on.
+ * Results are bit-identical to the per-step loop of kmpc_solve_mv_cap and kmpc_backtest_step.
+ *   max_turnover (run): NaN or < 0 KMPC_ERR_INVALID; 0: the call IS kmpc_markowitz_run with the
+ *               same arguments (its workspace rule too), bit-identical results.
+ *   max_turnover (sweep): [n_cfg] float64 DEVICE array, one cap per config. A config whose cap is not
+ *               finite or not > 0 ends every step KMPC_STATUS_SOLVER_ERROR with the hold fallback, as
+ *               one with a bad gamma[j] does: the host cannot see device values. A null pointer is
+ *               KMPC_ERR_INVALID with the other null arrays.
+ *   max_weight: as kmpc_markowitz_run (0: none, and then allow_short is allowed under the cap too).
+ *   workspace:  kmpc_mv_cap_workspace_bytes of mvdesc with B = P (sweep: n_cfg * P), 0 up to H*N = 128.
+ * Every other argument and rule, the n_steps = 0 shape probe and the P = 0 return as
+ * kmpc_markowitz_run / kmpc_markowitz_sweep. */
+int kmpc_markowitz_run_cap(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                           double max_turnover, int step0, int n_steps, const double* mu, const double* sigma,
+                           const int* valid, const float* realized, int n_real, double* weights, double* value,
+                           double* hist, double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                           void* stream);
+int kmpc_markowitz_sweep_cap(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                             int n_cfg, const double* gamma, const double* mv_cost, const double* bt_cost,
+                             const double* max_turnover /* [n_cfg], device */, int step0, int n_steps,
+                             const double* mu, const double* sigma, const int* valid, const float* realized,
+                             int n_real, double* weights, double* value, double* hist, double* target, int* status,
+                             double* obj, void* workspace, size_t ws_bytes, void* stream);
+
 /* Workspace needed by kmpc_rollout / kmpc_solve / kmpc_window (either desc may be NULL; with both,
    the sum for kmpc_window: rollout scratch + yhat + the solve's). */
 size_t kmpc_workspace_bytes(const kmpc_rollout_desc* rdesc, const kmpc_solve_desc* sdesc);
@@ -551,7 +607,10 @@ const char* kmpc_strerror(int code);
    functions, no struct, enum or existing function changed.
    kmpc_solve_box_workspace_bytes and kmpc_solve_box_ws were added within 0.7.0 in the same way: two
    new functions, no struct, enum or existing function changed (kmpc_solve_box keeps every return
-   code it had). */
+   code it had).
+   kmpc_mv_cap_workspace_bytes, kmpc_solve_mv_cap, kmpc_markowitz_run_cap and kmpc_markowitz_sweep_cap
+   were added within 0.7.0 in the same way: four new functions, no struct, enum or existing function
+   changed. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

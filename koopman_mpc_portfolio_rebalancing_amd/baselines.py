@@ -10,7 +10,8 @@ encoder / decoder and the latent operator A^T (row-vector convention, z <- z @ A
 
 Mirrors ``MarkowitzStrategy`` (baselines.py:24-106): the rolling 60-row mean / covariance of the
 de-standardized current returns (kmpc_rolling_moments) and the H = 1 mean-variance solve
-(kmpc_solve_mv, mpc.py:119-184; kmpc_solve_mv_box under a per-asset position limit) run on the
+(kmpc_solve_mv, mpc.py:119-184; kmpc_solve_mv_box under a per-asset position limit,
+kmpc_solve_mv_cap under an L1 turnover cap) run on the
 device, for one window (``rebalance``) or many (``rebalance_batch``). A whole Markowitz backtest of P
 paths runs on the device too (``run_markowitz_lockstep``: every step of a path in one
 kmpc_markowitz_run launch), as does a sweep of the baseline's two hyper-parameters over shared
@@ -29,7 +30,7 @@ from . import _lib
 from .backtest import (METRIC_NAMES, BacktestConfig, KoopmanMPCStrategy, Strategy, _cache_hit, _cache_key,
                        _env_stats, run_backtest)
 from .koopman import KoopmanModelSpec
-from .mpc import MPCConfig, _box_limit, _mv_desc, _workspace, solve_mpc_mean_variance_batched
+from .mpc import MPCConfig, _box_limit, _mv_desc, _mv_turnover_cap, _workspace, solve_mpc_mean_variance_batched
 
 
 def fit_dmd(train_data) -> np.ndarray:
@@ -104,13 +105,14 @@ def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None
 
 
 class _LimitKeyword(type(Strategy)):
-    """``MarkowitzStrategy(..., max_weight=u)``: the keyword is taken by the class call and applied
-    with ``set_max_weight`` — ``__init__`` keeps the reference's three arguments exactly
-    (baselines.py:33-37), as the drop-in surface promises."""
+    """``MarkowitzStrategy(..., max_weight=u, max_turnover=tau)``: the keywords are taken by the
+    class call and applied with ``set_max_weight`` / ``set_max_turnover`` — ``__init__`` keeps the
+    reference's three arguments exactly (baselines.py:33-37), as the drop-in surface promises."""
 
-    def __call__(cls, *args, max_weight: float = 0.0, **kwargs):
+    def __call__(cls, *args, max_weight: float = 0.0, max_turnover: float = 0.0, **kwargs):
         obj = super().__call__(*args, **kwargs)
         obj.set_max_weight(max_weight)
+        obj.set_max_turnover(max_turnover)
         return obj
 
 
@@ -122,7 +124,11 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
     of the last ``lookback_window`` rows, W[0] of the mean-variance solve). ``max_weight`` (keyword,
     not in the reference) is the per-asset position limit of ``MPCConfig.max_weight``: every target
     keeps w <= max_weight (long-only, N * max_weight > 1; 0: none), so the baseline runs under the
-    same limit as the MPC strategies.
+    same limit as the MPC strategies. ``max_turnover`` (keyword, not in the reference either) is
+    the L1 turnover cap of ``MPCConfig.mv_max_turnover``: every target keeps
+    ||w - current_weights||_1 <= max_turnover (0: none, the reference's program), the cap the MPC
+    strategies trade under (MPCConfig.max_turnover). A step whose current weights lie further than
+    the cap from the feasible set (under a position limit only) holds them.
     """
 
     def __init__(self, risk_aversion: float = 1.0, cost_coeff: float = 0.001, allow_short: bool = False):
@@ -130,6 +136,7 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         self.cost_coeff = cost_coeff
         self.allow_short = allow_short
         self.max_weight = 0.0
+        self.max_turnover = 0.0
         self.mpc_config = MPCConfig(horizon=1, gamma=risk_aversion, cost_coeff=cost_coeff,
                                     allow_short=allow_short, solver="ECOS")
         self._dev = None
@@ -139,6 +146,11 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         """Set the per-asset position limit on the strategy and in its ``mpc_config``."""
         self.max_weight = max_weight
         self.mpc_config.max_weight = max_weight
+
+    def set_max_turnover(self, max_turnover: float) -> None:
+        """Set the L1 turnover cap on the strategy and in its ``mpc_config`` (mv_max_turnover)."""
+        self.max_turnover = max_turnover
+        self.mpc_config.mv_max_turnover = max_turnover
 
     def _device(self) -> torch.device:
         if self._dev is None:
@@ -212,6 +224,7 @@ def _markowitz_paths(strategy, obs, realized, config: BacktestConfig, mean, std,
     P, T, N = (int(v) for v in r.shape)
     H = int(strategy.mpc_config.horizon)
     u = _box_limit(strategy.mpc_config, N)
+    tau = _mv_turnover_cap(strategy.mpc_config)
     n_rows = T if n_rows is None else int(n_rows)
     steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
     dev = strategy._device()
@@ -221,7 +234,7 @@ def _markowitz_paths(strategy, obs, realized, config: BacktestConfig, mean, std,
     sd = torch.as_tensor(np.asarray(std, np.float64).astype(np.float32), device=dev)
     if m.numel() != N or sd.numel() != N:
         raise ValueError(f"mean and std must have {N} entries")
-    return SimpleNamespace(z=z, rt=rt, P=P, T=T, N=N, H=H, u=u, steps=steps, S=len(steps), dev=dev, m=m, sd=sd,
+    return SimpleNamespace(z=z, rt=rt, P=P, T=T, N=N, H=H, u=u, tau=tau, steps=steps, S=len(steps), dev=dev, m=m, sd=sd,
                            ts=torch.as_tensor(steps, dtype=torch.int32, device=dev))
 
 
@@ -265,8 +278,8 @@ def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config:
     realized log-returns are realized[p]. Arguments and the returned dict as run_backtest_lockstep.
 
     Args:
-        strategy: a MarkowitzStrategy (risk_aversion, cost_coeff, allow_short, max_weight; the
-            horizon of its mpc_config, 1 in the reference).
+        strategy: a MarkowitzStrategy (risk_aversion, cost_coeff, allow_short, max_weight,
+            max_turnover; the horizon of its mpc_config, 1 in the reference).
         obs: [P, T, >= N] float32 standardized test rows; the first N columns are the current returns.
         realized: [P, T, N] float32 de-standardized log-returns (the reference's all_returns).
         mean, std: [N] de-standardisation of the moments (env.stats).
@@ -274,7 +287,8 @@ def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config:
             config.rebalance_freq), step t realizing row t + 1.
         persistent: every step of a path in one launch per chunk of steps (kmpc_markowitz_run: the
             step's solve or hold, then its bookkeeping, back to back in one workgroup per path).
-            False: the per-step loop — kmpc_solve_mv_ws / kmpc_solve_mv_box over the P windows, the
+            False: the per-step loop — kmpc_solve_mv_ws / kmpc_solve_mv_box (kmpc_solve_mv_cap under
+            a turnover cap, where the persistent kernel is kmpc_markowitz_run_cap) over the P windows, the
             hold select, kmpc_backtest_step. Default: the persistent kernel wherever the C ABI has it
             (H * N <= 1,024). The two are bit-identical.
     The steps go in chunks of _markowitz_chunk(P, N), one kmpc_rolling_moments_paths each.
@@ -293,9 +307,13 @@ def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config:
     md = _mv_desc(P, N, H, strategy.mpc_config, False)
     with torch.cuda.device(dev):
         sh = _lib.stream_handle(dev)
+        # under a turnover cap the _cap entry with its cap ahead of the steps, and its workspace query
+        run, head, query = L.kmpc_markowitz_run, (ctypes.byref(bd), ctypes.byref(md), pp.u), L.kmpc_mv_workspace_bytes
+        if pp.tau:
+            run, head, query = L.kmpc_markowitz_run_cap, head + (pp.tau,), L.kmpc_mv_cap_workspace_bytes
         if persistent is None or persistent:
-            rc = L.kmpc_markowitz_run(ctypes.byref(bd), ctypes.byref(md), pp.u, 0, 0, None, None, None, None, 0,
-                                      None, None, None, None, None, None, None, 0, sh)   # (shape check only)
+            rc = run(*head, 0, 0, None, None, None, None, 0,
+                     None, None, None, None, None, None, None, 0, sh)   # (shape check only)
             if rc == _lib.KMPC_ERR_UNSUPPORTED and persistent is None:
                 persistent = False
             elif rc == _lib.KMPC_ERR_UNSUPPORTED:
@@ -307,11 +325,11 @@ def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config:
             target = torch.empty((P, N), **f64)
             status = torch.zeros((P,), dtype=torch.int32, device=dev)
             objv = torch.empty((P,), **f64)
-            nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(md)))
+            nws = int(query(ctypes.byref(md)))
             ws = _workspace(dev, nws) if nws else None
             for k0, n, mu, sigma, valid, rr, n_real in _markowitz_chunks(pp, lookback_window):
-                _lib.check(L.kmpc_markowitz_run(
-                    ctypes.byref(bd), ctypes.byref(md), pp.u, k0, n, mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(),
+                _lib.check(run(
+                    *head, k0, n, mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(),
                     rr.data_ptr() if rr is not None else None, n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(),
                     target.data_ptr(), status.data_ptr(), objv.data_ptr(), ws.data_ptr() if ws is not None else None,
                     nws, sh))
@@ -331,7 +349,7 @@ def run_markowitz_lockstep(strategy: "MarkowitzStrategy", obs, realized, config:
 def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: BacktestConfig, mean, std,
                         risk_aversions: Sequence[float], cost_coeffs: Sequence[float],
                         bt_cost_coeffs: Optional[Sequence[float]] = None, n_rows: Optional[int] = None,
-                        lookback_window: int = 60) -> Dict[str, Any]:
+                        lookback_window: int = 60, max_turnovers: Optional[Sequence[float]] = None) -> Dict[str, Any]:
     """A hyper-parameter sweep of run_markowitz_lockstep: C configs (risk_aversion, the strategy's
     cost_coeff, BacktestConfig.cost_coeff) over the same P paths, every step of every (config, path)
     in kmpc_markowitz_sweep launches, one workgroup each. The moments depend on the path only: they
@@ -343,6 +361,9 @@ def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: Ba
         obs, realized, config, mean, std, n_rows, lookback_window: as run_markowitz_lockstep.
         risk_aversions, cost_coeffs: [C] each (ValueError on unequal lengths or none).
         bt_cost_coeffs: the bookkeeping's cost_coeff per config (default config.cost_coeff for all).
+        max_turnovers: the turnover cap per config [C] (kmpc_markowitz_sweep_cap). Default: the
+            strategy's cap for every config (none: the uncapped sweep). Given, every config is a
+            capped one: a cap that is not finite or not > 0 holds, as below.
     A config with a negative or non-finite risk_aversion or cost_coeff holds its weights at every
     step (turnover and cost 0); the others are not affected. Config j's rows equal
     run_markowitz_lockstep with that config's parameters bit for bit.
@@ -360,6 +381,9 @@ def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: Ba
     btc = [float(config.cost_coeff)] * C if bt_cost_coeffs is None else [float(v) for v in bt_cost_coeffs]
     if len(btc) != C:
         raise ValueError(f"bt_cost_coeffs has {len(btc)} entries for {C} configs")
+    caps = None if max_turnovers is None else [float(v) for v in max_turnovers]
+    if caps is not None and len(caps) != C:
+        raise ValueError(f"max_turnovers has {len(caps)} entries for {C} configs")
     pp = _markowitz_paths(strategy, obs, realized, config, mean, std, n_rows)
     P, N, H, S, dev = pp.P, pp.N, pp.H, pp.S, pp.dev
     f64 = dict(dtype=torch.float64, device=dev)
@@ -374,14 +398,21 @@ def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: Ba
         with torch.cuda.device(dev):
             sh = _lib.stream_handle(dev)
             pg, pc, pb = (torch.tensor(v, **f64) for v in (ga, mc, btc))
+            if caps is None and pp.tau:
+                caps = [pp.tau] * C
+            sweep, head, query = L.kmpc_markowitz_sweep, (pg.data_ptr(), pc.data_ptr(), pb.data_ptr()), \
+                L.kmpc_mv_workspace_bytes
+            if caps is not None:
+                pt = torch.tensor(caps, **f64)
+                sweep, head, query = L.kmpc_markowitz_sweep_cap, head + (pt.data_ptr(),), L.kmpc_mv_cap_workspace_bytes
             target = torch.empty((C * P, N), **f64)
             status = torch.zeros((C * P,), dtype=torch.int32, device=dev)
             objv = torch.empty((C * P,), **f64)
-            nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(md)))
+            nws = int(query(ctypes.byref(md)))
             ws = _workspace(dev, nws) if nws else None
             for k0, n, mu, sigma, valid, rr, n_real in _markowitz_chunks(pp, lookback_window):
-                _lib.check(L.kmpc_markowitz_sweep(
-                    ctypes.byref(bd), ctypes.byref(md), pp.u, C, pg.data_ptr(), pc.data_ptr(), pb.data_ptr(), k0, n,
+                _lib.check(sweep(
+                    ctypes.byref(bd), ctypes.byref(md), pp.u, C, *head, k0, n,
                     mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), rr.data_ptr() if rr is not None else None,
                     n_real, w.data_ptr(), value.data_ptr(), hist.data_ptr(), target.data_ptr(), status.data_ptr(),
                     objv.data_ptr(), ws.data_ptr() if ws is not None else None, nws, sh))
@@ -395,8 +426,8 @@ def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: Ba
 def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Sequence["MarkowitzStrategy"]) -> list:
     """run_backtest(strategies[j], env, config) for C Markowitz strategies on one environment in one
     sweep (run_markowitz_sweep with P = 1): the env-level counterpart of sweep_backtest. The
-    strategies may differ in risk_aversion and cost_coeff only (ValueError otherwise, before any
-    device work). Returns C DataFrames with the reference's columns (date, portfolio_value, return,
+    strategies may differ in risk_aversion, cost_coeff and max_turnover only, and must be all capped
+    or all uncapped (ValueError otherwise, before any device work). Returns C DataFrames with the reference's columns (date, portfolio_value, return,
     turnover, cost), the rebalance_freq quirk kept. An env without stats (custom de-standardisation)
     runs run_backtest per strategy."""
     strats = list(strategies)
@@ -407,10 +438,13 @@ def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Seque
         for name in ("allow_short", "max_weight"):
             if getattr(s, name) != getattr(s0, name):
                 raise ValueError(f"strategies[{j}] differs from strategies[0] in {name}: a sweep varies "
-                                 "risk_aversion and cost_coeff only")
+                                 "risk_aversion, cost_coeff and max_turnover only")
+        if bool(_mv_turnover_cap(s.mpc_config)) != bool(_mv_turnover_cap(s0.mpc_config)):
+            raise ValueError(f"strategies[{j}] and strategies[0]: one has a turnover cap and one has none; a sweep "
+                             "runs capped strategies or uncapped ones")
         if int(s.mpc_config.horizon) != int(s0.mpc_config.horizon):
             raise ValueError(f"strategies[{j}] differs from strategies[0] in horizon: a sweep varies "
-                             "risk_aversion and cost_coeff only")
+                             "risk_aversion, cost_coeff and max_turnover only")
     st = _env_stats(env)
     n = getattr(env, "n_assets", None)
     if st is None or n is None:
@@ -419,7 +453,8 @@ def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Seque
     rets = env.destandardize_returns(env.extract_current_returns(data))
     n_rows = len(env.test_dataset)
     out = run_markowitz_sweep(s0, torch.as_tensor(data)[None], torch.as_tensor(rets)[None], config, st[0], st[1],
-                              [s.risk_aversion for s in strats], [s.cost_coeff for s in strats], n_rows=n_rows)
+                              [s.risk_aversion for s in strats], [s.cost_coeff for s in strats], n_rows=n_rows,
+                              max_turnovers=[s.max_turnover for s in strats] if s0.max_turnover else None)
     steps = range(0, n_rows - config.horizon, config.rebalance_freq)
     dates = [env.test_dataset.dates[t] for t in steps]
     cols = {k: out[k][:, 0].cpu().numpy() for k in ("portfolio_value", "return", "turnover", "cost")}

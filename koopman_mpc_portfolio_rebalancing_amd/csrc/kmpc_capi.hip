@@ -332,6 +332,34 @@ int kmpc_solve_mv_box(const kmpc_mv_desc* desc, double max_weight, const double*
                                  ws_bytes, (hipStream_t)stream, u);
 }
 
+size_t kmpc_mv_cap_workspace_bytes(const kmpc_mv_desc* desc) { return kmpc::mv_cap_workspace_bytes(desc); }
+
+int kmpc_solve_mv_cap(const kmpc_mv_desc* desc, double max_weight, double max_turnover, const double* mu,
+                      const double* sigma, size_t sigma_stride, const double* w_prev, double* w_out, int* status,
+                      double* obj, int* iters, void* workspace, size_t ws_bytes, void* stream) {
+    // every rule is decided before any launch (and before the B == 0 return): the descriptor as
+    // kmpc_solve_mv_ws, the cap, then the limit (0: none) in mv_box_limit's order
+    if (!desc || desc->B < 0 || desc->N < 1 || desc->H < 1) return KMPC_ERR_INVALID;
+    if (desc->H > KMPC_MV_MAX_H || desc->N * desc->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (!(max_turnover >= 0.0)) return KMPC_ERR_INVALID;                // (NaN too)
+    if (max_turnover == 0.0) {   // no cap: the existing call
+        if (max_weight == 0.0)
+            return kmpc_solve_mv_ws(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
+                                    ws_bytes, stream);
+        return kmpc_solve_mv_box(desc, max_weight, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters,
+                                 workspace, ws_bytes, stream);
+    }
+    double u = 0.0;
+    if (max_weight != 0.0) {   // (0: none, and then allow_short is allowed)
+        const int rc = mv_box_limit(*desc, max_weight, u);
+        if (rc) return rc;
+    }
+    if (desc->B == 0) return KMPC_OK;
+    if (!mu || !sigma || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
+    return kmpc::mv_solve_launch(desc, mu, sigma, sigma_stride, w_prev, w_out, status, obj, iters, workspace,
+                                 ws_bytes, (hipStream_t)stream, u, max_turnover);
+}
+
 int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int ldz,
                          const float* mean, const float* std, const int* ts,
                          double* mu, double* sigma, int* valid, void* stream) {
@@ -359,9 +387,10 @@ namespace {
 
 // kmpc_markowitz_run (the batch is the paths) and kmpc_markowitz_sweep (configs x paths; the configs
 // carry gamma and the two cost coefficients, the descs' are not read). Every rule is decided before
-// any launch, the position limit's in kmpc_solve_mv_box's order.
-int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
-                    const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
+// any launch, the position limit's in kmpc_solve_mv_box's order. cap: the _cap entries — the run's
+// max_turnover (NaN or < 0 invalid; 0 is the plain run) or the sweep's per-config caps (device).
+int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, bool cap,
+                    double max_turnover, const double* cfg_turnover, int n_cfg, const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
                     const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
                     double* weights, double* value, double* hist, double* target, int* status, double* obj,
                     void* workspace, size_t ws_bytes, void* stream) {
@@ -371,6 +400,10 @@ int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc
         return KMPC_ERR_INVALID;
     if (sweep && (n_cfg < 1 || (long long)n_cfg * bd->P > 0x7fffffffLL)) return KMPC_ERR_INVALID;
     if (d->H > KMPC_MV_MAX_H || (long long)d->N * d->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (cap && !sweep) {
+        if (!(max_turnover >= 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+        cap = max_turnover > 0.0;                                // 0: kmpc_markowitz_run
+    }
     double u = 0.0;   // the active limit (0: the plain kernels)
     if (max_weight != 0.0) {   // (0: none, for these two entries only)
         const int rc = mv_box_limit(*d, max_weight, u);
@@ -378,9 +411,9 @@ int markowitz_entry(bool sweep, const kmpc_backtest_desc* bd, const kmpc_mv_desc
     }
     if (bd->P == 0 || n_steps == 0) return KMPC_OK;
     if (!mu || !sigma || !valid || !weights || !value || !hist || !target || !status || !obj ||
-        (n_real > 0 && !realized) || (sweep && (!gamma || !mv_cost || !bt_cost)))
+        (n_real > 0 && !realized) || (sweep && (!gamma || !mv_cost || !bt_cost)) || (sweep && cap && !cfg_turnover))
         return KMPC_ERR_INVALID;
-    return kmpc::mv_bt_launch(bd, d, u, sweep ? n_cfg : 0, gamma, mv_cost, bt_cost, step0, n_steps, mu, sigma, valid,
+    return kmpc::mv_bt_launch(bd, d, u, cap, max_turnover, cfg_turnover, sweep ? n_cfg : 0, gamma, mv_cost, bt_cost, step0, n_steps, mu, sigma, valid,
                               realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
                               (hipStream_t)stream);
 }
@@ -393,9 +426,19 @@ int kmpc_markowitz_run(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvde
                        int n_steps, const double* mu, const double* sigma, const int* valid, const float* realized,
                        int n_real, double* weights, double* value, double* hist, double* target, int* status,
                        double* obj, void* workspace, size_t ws_bytes, void* stream) {
-    return markowitz_entry(false, bdesc, mvdesc, max_weight, 0, nullptr, nullptr, nullptr, step0, n_steps, mu, sigma,
-                           valid, realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
-                           stream);
+    return markowitz_entry(false, bdesc, mvdesc, max_weight, false, 0.0, nullptr, 0, nullptr, nullptr, nullptr, step0,
+                           n_steps, mu, sigma, valid, realized, n_real, weights, value, hist, target, status, obj,
+                           workspace, ws_bytes, stream);
+}
+
+int kmpc_markowitz_run_cap(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                           double max_turnover, int step0, int n_steps, const double* mu, const double* sigma,
+                           const int* valid, const float* realized, int n_real, double* weights, double* value,
+                           double* hist, double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                           void* stream) {
+    return markowitz_entry(false, bdesc, mvdesc, max_weight, true, max_turnover, nullptr, 0, nullptr, nullptr, nullptr,
+                           step0, n_steps, mu, sigma, valid, realized, n_real, weights, value, hist, target, status,
+                           obj, workspace, ws_bytes, stream);
 }
 
 int kmpc_markowitz_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight, int n_cfg,
@@ -403,9 +446,20 @@ int kmpc_markowitz_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mv
                          const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
                          double* weights, double* value, double* hist, double* target, int* status, double* obj,
                          void* workspace, size_t ws_bytes, void* stream) {
-    return markowitz_entry(true, bdesc, mvdesc, max_weight, n_cfg, gamma, mv_cost, bt_cost, step0, n_steps, mu, sigma,
-                           valid, realized, n_real, weights, value, hist, target, status, obj, workspace, ws_bytes,
-                           stream);
+    return markowitz_entry(true, bdesc, mvdesc, max_weight, false, 0.0, nullptr, n_cfg, gamma, mv_cost, bt_cost, step0,
+                           n_steps, mu, sigma, valid, realized, n_real, weights, value, hist, target, status, obj,
+                           workspace, ws_bytes, stream);
+}
+
+int kmpc_markowitz_sweep_cap(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                             int n_cfg, const double* gamma, const double* mv_cost, const double* bt_cost,
+                             const double* max_turnover, int step0, int n_steps, const double* mu,
+                             const double* sigma, const int* valid, const float* realized, int n_real,
+                             double* weights, double* value, double* hist, double* target, int* status, double* obj,
+                             void* workspace, size_t ws_bytes, void* stream) {
+    return markowitz_entry(true, bdesc, mvdesc, max_weight, true, 0.0, max_turnover, n_cfg, gamma, mv_cost, bt_cost,
+                           step0, n_steps, mu, sigma, valid, realized, n_real, weights, value, hist, target, status,
+                           obj, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -41,17 +41,21 @@ int standardize_launch(int T, int N, const double* y, const double* mean, const 
 // kmpc_mv.hip
 size_t mv_lds_bytes(int N, int H);
 size_t mv_workspace_bytes(const kmpc_mv_desc* d);
+size_t mv_cap_workspace_bytes(const kmpc_mv_desc* d);   // the CAP kernels' slabs (0 while H N <= 128)
 int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma, size_t sigma_stride,
                     const double* w_prev, double* w_out, int* status, double* obj, int* iters,
-                    void* ws, size_t ws_bytes, hipStream_t stream, double max_weight = 0.0);   // > 0: the BOX kernels
+                    void* ws, size_t ws_bytes, hipStream_t stream, double max_weight = 0.0,   // > 0: the BOX kernels
+                    double max_turnover = 0.0);   // > 0: the CAP kernels (workspace: mv_cap_workspace_bytes)
 int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, int ldz, const float* mean,
                            const float* stdv, const int* ts, double* mu, double* sigma, int* valid,
                            hipStream_t stream);
 int rolling_moments_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
                                  const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
                                  int* valid, hipStream_t stream);
-// the Markowitz backtest: the run (n_cfg = 0) or the sweep of n_cfg configs
-int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
+// the Markowitz backtest: the run (n_cfg = 0) or the sweep of n_cfg configs; cap: the CAP kernels with
+// the run's max_turnover or the sweep's per-config caps cfg_turnover [n_cfg] (device)
+int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, bool cap,
+                 double max_turnover, const double* cfg_turnover, int n_cfg,
                  const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
                  const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
                  double* weights, double* value, double* hist, double* target, int* status, double* obj,

@@ -5,7 +5,8 @@
 // Program per window (mpc.py:128, 145-172):
 //   maximize  sum_t [ w_t . mu_t - gamma w_t' Sigma w_t ] - c sum_t ||w_t - w_{t-1}||_1
 //   s.t.      1'w_t = 1, w_t >= 0 unless allow_short          (no turnover cap), w_{-1} = w_prev;
-//             with a position limit (kmpc_solve_mv_box, the BOX kernels) also w_t <= u, long-only.
+//             with a position limit (kmpc_solve_mv_box, the BOX kernels) also w_t <= u, long-only;
+//             with a turnover cap (kmpc_solve_mv_cap, the CAP kernels) also ||w_t - w_{t-1}||_1 <= tau.
 // One workgroup per window, one element (t, i) of W per thread (n = H N <= 1024). Algorithm:
 // Mehrotra predictor-corrector primal-dual interior point on the epigraph form (s_ti >= |d_ti|,
 // d = w_t - w_{t-1}), float64, objective scaled by max(|mu|, 2 gamma |Sigma|, c). The s rows and
@@ -47,6 +48,7 @@ struct MvArgs {
     double* ws;             // workspace slabs (global-M variant)
     size_t slab;            // doubles per slab
     double max_weight;      // BOX kernels: the per-asset position limit u (w <= u), N u > 1
+    double max_turnover;    // CAP kernels: the turnover cap tau (||w_t - w_{t-1}||_1 <= tau), > 0
 };
 
 constexpr int MV_SLOTS = 512;   // windows in flight of the global-M variant
@@ -147,24 +149,70 @@ __device__ double chol_solve(const double* M, int n, double b, double* vec) {
     return out;
 }
 
+// CAP kernels: feasibility of period 0 and the start point; returns the iteration bound. p is w_prev clipped
+// to the bounds, out = ||p - w_prev||_1 and d0 = out + |1 - 1'p| the L1 distance from w_prev to the
+// feasible set: d0 > tau has no feasible point (-1: infeasible), and a tau outside the program (not
+// finite, not > 0: only the sweep can carry one) runs no iteration (0: solver error). Else the plain
+// start w (on entry) is pulled towards p, w = p + theta (w - p) with
+// theta = min(1, 0.5 (tau - out) / ||w - p||_1), so that ||w - w_prev||_1 <= out + 0.5 (tau - out) < tau.
+template <bool BOX>
+__device__ __forceinline__ int capped_start(const MvArgs& a, double wpi, bool act, int k, double* red, double& w) {
+    const int N = a.N;
+    const double tau = a.max_turnover;
+    double p = a.allow_short ? wpi : fmax(wpi, 0.0);
+    if constexpr (BOX) p = fmin(p, a.max_weight);
+    const double out = block_sum(k < N ? fabs(p - wpi) : 0.0, red);
+    const double d0 = out + fabs(1.0 - block_sum(k < N ? p : 0.0, red));
+    const double dist = block_sum(k < N ? fabs(w - p) : 0.0, red);
+    const double theta = dist > 0.0 ? fmin(1.0, 0.5 * (tau - out) / dist) : 1.0;
+    if (act) w = p + theta * (w - p);
+    if (!(tau > 0.0) || !isfinite(tau)) return 0;
+    return d0 > tau ? -1 : a.max_iter;
+}
 
 // One window. GM: M and Y in the block's workspace slab (else in LDS after the small arrays).
 // BOX: the position limit w <= u (long-only callers), one more barrier on w treated as w >= 0 is:
 // slack x5 = u - w taken from the iterate (no slack variable), multiplier l5 in a register.
-template <bool GM, bool BOX>
+// CAP: the turnover cap, one more inequality per period on the s rows (present at c = 0 too):
+// slack x6_t = tau - sum_i s_t,i kept as a variable (as z2, z3), multiplier l6_t, both in LDS (lane
+// t < H works on period t's). Eliminating s leaves (al + be) ds + (be - al) dd + dl6_t = qs, so dl6
+// enters the w equation through C' = -D' diag(g), g = (be - al) P (one column per period), and the
+// cap row reads C dw - kap dl6 = r3 with kap_t = x6_t / l6_t + sum_i P_t,i and
+// r3_t = -sum_i P qs + rg6_t + rc6_t / l6_t:
+//   M dw + A' dnu + C' dl6 = r,  A dw = r2,  C dw - kap dl6 = r3
+// M and its Cholesky are the same; Y grows to [A' C'] (2H columns) and the Schur system to the SPD
+// 2H x 2H matrix [A; C] M^{-1} [A' C'] + diag(0, kap) (dnu then holds [dnu; dl6]). Period 0 is
+// feasible iff d0 <= tau, d0 the L1 distance from w_prev to the budget plane within the bounds
+// (later periods can always hold): d0 > tau is KMPC_STATUS_INFEASIBLE before any iteration.
+// The statements the CAP = false forms run are left word for word as they were and the CAP form
+// overrides them under if constexpr (the start's s, z2, z3; the loop bound): even a local for 1 / N
+// changed which of two products the compiler fuses there, and with it the uncapped results' last bits.
+template <bool GM, bool BOX, bool CAP>
 __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     const int N = a.N, H = a.H, n = N * H;
+    constexpr int SH = CAP ? 2 : 1, XH = CAP ? 13 : 4;   // Schur rows per period; H-vectors after Sm
+    const int H2 = SH * H;
     double* vec = lds;                      // [n] broadcast vector
-    double* Sm = vec + n;                   // [H][H] A M^{-1} A', then its Cholesky factor
-    double* idg = Sm + H * H + 4 * H + 18;  // [n] 1 / L_jj of the Cholesky factor
+    double* Sm = vec + n;                   // [H2][H2] the Schur complement, then its Cholesky factor
+    double* idg = Sm + H2 * H2 + XH * H + 18;  // [n] 1 / L_jj of the Cholesky factor
     double* M = GM ? a.ws + (size_t)blockIdx.x * a.slab : idg + n;   // packed lower: M, then L
-    double* Y = M + tri(n, 0);              // [H][n] M^{-1} A'
-    double* pv = Sm + H * H;                // [H] period sums (after Sm in LDS, both variants)
+    double* Y = M + tri(n, 0);              // [H2][n] M^{-1} A' (CAP: M^{-1} [A' C'])
+    double* pv = Sm + H2 * H2;              // [H] period sums (after Sm in LDS, both variants)
     double* nu = pv + H;                    // [H] budget multipliers
-    double* dnu = nu + H;                   // [H]
-    double* rpv = dnu + H;                  // [H] primal residuals 1'w_t - 1
+    double* dnu = nu + H;                   // [H2] (CAP: dl6 after dnu)
+    double* rpv = dnu + H2;                 // [H] primal residuals 1'w_t - 1
     double* red = rpv + H;                  // [16] reduction slots (one per wave)
     int* flag = (int*)(red + 16);
+    // CAP only, [H] each after the flag's slot: the cap rows' slack, multiplier, complementarity
+    // target, residual, slack step, kap, a second set of period sums, the Schur right-hand side
+    double* x6 = red + 18;
+    double* l6 = x6 + H;
+    double* rc6 = l6 + H;
+    double* rg6 = rc6 + H;
+    double* dx6 = rg6 + H;
+    double* kap = dx6 + H;
+    double* pc = kap + H;
+    double* cx = pc + H;
 
     const int k = threadIdx.x;
     const bool act = k < n;
@@ -172,7 +220,7 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     const double* Sig = a.sigma + a.sigma_stride * (size_t)b;
     const double* wpv = a.wp + (size_t)b * N;
     const double* muv = a.mu + (size_t)b * n;
-    const bool hw = !a.allow_short, hs = a.c > 0.0;
+    const bool hw = !a.allow_short, hs = a.c > 0.0 || CAP;
     const double wpi = act ? wpv[i] : 0.0;
     const double mk = act ? muv[k] : 0.0;
     double* wout = a.wout + (size_t)b * (a.return_full ? n : N);
@@ -213,18 +261,37 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     } else if (nonfinite == 0.0 && isfinite(a.gamma) && isfinite(a.c)) {
         double w = act ? 0.5 * (hw ? fmax(wpi, 0.0) : wpi) + 0.5 / N : 0.0;
         if constexpr (BOX) w = fmin(w, 0.5 * (a.max_weight + 1.0 / N));   // strictly inside: 1 / N < u
+        int cap_iter = 0;   // CAP: the iteration bound of capped_start
+        double sfl = 0.0;   // CAP: s above |d| at the start
+        if constexpr (CAP) {
+            // s_t,i = |d_t,i| + half of what the start leaves of tau, shared equally: sum_i s_t,i < tau
+            cap_iter = capped_start<BOX>(a, wpi, act, k, red, w);
+            const double D0 = block_sum(k < N ? fabs(w - wpi) : 0.0, red);
+            sfl = 0.5 * (a.max_turnover - D0) / N;
+        }
         double wm = prev_period(w, vec, k, n, N, wpi);
         double s = (act && hs) ? fabs(w - wm) + 1.0 / N : 0.0;
         // slacks of the two |d| rows kept as variables (no cancellation in s -+ d near the optimum)
         double z2 = (act && hs) ? fmax(s - (w - wm), 1e-2) : 1.0, z3 = (act && hs) ? fmax(s + (w - wm), 1e-2) : 1.0;
+        if constexpr (CAP) {   // ... and the slacks' floor scaled to a small tau
+            const double zlo = 1e-2 * fmin(1.0, a.max_turnover);
+            s = act ? fabs(w - wm) + sfl : 0.0;
+            z2 = act ? fmax(s - (w - wm), zlo) : 1.0;
+            z3 = act ? fmax(s + (w - wm), zlo) : 1.0;
+            period_sums(s, vec, pv, k, n, N, H);
+            if (k < H) { x6[k] = fmax(a.max_turnover - pv[k], zlo); l6[k] = 1.0; }
+        }
         double l1 = (act && hw) ? 1.0 : 0.0, l2 = (act && hs) ? 1.0 : 0.0, l3 = l2;
         double l5 = 0.0, x5 = 1.0;   // BOX only (l5 stays 0 on the inactive lanes)
         if constexpr (BOX) l5 = act ? 1.0 : 0.0;
         if (k < H) nu[k] = 0.0;
-        const int mcon = (hw ? n : 0) + (hs ? 2 * n : 0) + (BOX ? n : 0);
+        const int mcon = (hw ? n : 0) + (hs ? 2 * n : 0) + (BOX ? n : 0) + (CAP ? H : 0);
         const double inv_m = 1.0 / (mcon > 0 ? mcon : 1);
 
         for (it = 0; it < a.max_iter; ++it) {
+            if constexpr (CAP) {
+                if (it >= cap_iter) break;   // (no iteration where the window is infeasible or tau outside the program)
+            }
             // ---- residuals ----
             wm = prev_period(w, vec, k, n, N, wpi);   // vec holds w afterwards
             double Sw = 0.0;
@@ -244,20 +311,31 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             const double rg2 = (act && hs) ? (s - d) - z2 : 0.0, rg3 = (act && hs) ? (s + d) - z3 : 0.0;
             const double eta = l2 - l3;
             const double etan = next_period(eta, vec, k, n, N);
+            if constexpr (CAP) {
+                period_sums(s, vec, pv, k, n, N, H);
+                if (k < H) rg6[k] = (a.max_turnover - pv[k]) - x6[k];
+            }
             period_sums(w, vec, pv, k, n, N, H);
             if (k < H) rpv[k] = pv[k] - 1.0;
             double prmax = 0.0;
             for (int q = 0; q < H; ++q) prmax = fmax(prmax, fabs(pv[q] - 1.0));
             double rw = act ? -mus + g2 * Sw - l1 + eta - etan + nu[t] : 0.0;
-            const double rs = (act && hs) ? cs - l2 - l3 : 0.0;
+            double rs = (act && hs) ? cs - l2 - l3 : 0.0;
             double comp = act ? w * l1 + z2 * l2 + z3 * l3 : 0.0;
+            double r6 = 0.0;   // CAP: |rg6| of the lane's period
+            if constexpr (CAP) {
+                if (act) rs += l6[t];
+                if (k < H) { comp += x6[k] * l6[k]; r6 = fabs(rg6[k]); }
+            }
             if constexpr (BOX) {
                 x5 = a.max_weight - w;
                 rw += l5;
                 comp += x5 * l5;
             }
             const double mu_c = block_sum(comp, red) * inv_m;
-            const double rd = block_max(fmax(fmax(fabs(rw), fabs(rs)), fmax(fabs(rg2), fabs(rg3))), red);
+            double rdl = fmax(fmax(fabs(rw), fabs(rs)), fmax(fabs(rg2), fabs(rg3)));
+            if constexpr (CAP) rdl = fmax(rdl, r6);
+            const double rd = block_max(rdl, red);
             const double wabs = block_max(act ? fabs(w) : 0.0, red);
             const double merit = fmax(mu_c, fmax(rd, prmax));
             if (!isfinite(merit)) break;
@@ -335,26 +413,43 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             }
             __syncthreads();
             if (*flag) break;
-            // Y = M^{-1} A' (one column per period) and S = A Y
-            for (int q = 0; q < H; ++q) {
-                const double bq = (act && t == q) ? 1.0 : 0.0;
+            // Y = M^{-1} A' (one column per period) and S = A Y; CAP: Y = M^{-1} [A' C'] and
+            // S = [A; C] Y + diag(0, kap), with (C y)_t = -sum_i g (y_t - y_{t-1})
+            double g = 0.0, gn = 0.0;
+            if constexpr (CAP) {
+                g = (be - al) * P;
+                gn = next_period(g, vec, k, n, N);
+                period_sums(P, vec, pv, k, n, N, H);
+                if (k < H) kap[k] = x6[k] / l6[k] + pv[k];
+            }
+            for (int q = 0; q < H2; ++q) {
+                double bq = (act && t == q) ? 1.0 : 0.0;
+                if constexpr (CAP) {
+                    if (q >= H) bq = act ? (t + 1 == q - H ? gn : 0.0) - (t == q - H ? g : 0.0) : 0.0;
+                }
                 const double yq = chol_solve(M, n, bq, vec);
                 if (act) Y[(size_t)q * n + k] = yq;
                 period_sums(yq, vec, pv, k, n, N, H);
-                if (k < H) Sm[k * H + q] = pv[k];
+                if (k < H) Sm[k * H2 + q] = pv[k];
                 __syncthreads();
+                if constexpr (CAP) {
+                    const double ym = prev_period(yq, vec, k, n, N, 0.0);
+                    period_sums(act ? -g * (yq - ym) : 0.0, vec, pv, k, n, N, H);
+                    if (k < H) Sm[(H + k) * H2 + q] = pv[k] + (q == H + k ? kap[k] : 0.0);
+                    __syncthreads();
+                }
             }
-            if (k == 0) {   // Cholesky of the H x H Schur complement
-                for (int j = 0; j < H; ++j) {
-                    double dj = Sm[j * H + j];
-                    for (int q = 0; q < j; ++q) dj -= Sm[j * H + q] * Sm[j * H + q];
+            if (k == 0) {   // Cholesky of the H2 x H2 Schur complement
+                for (int j = 0; j < H2; ++j) {
+                    double dj = Sm[j * H2 + j];
+                    for (int q = 0; q < j; ++q) dj -= Sm[j * H2 + q] * Sm[j * H2 + q];
                     if (!(dj > 0.0) || !isfinite(dj)) *flag = 1;
                     dj = sqrt(fmax(dj, 1e-300));
-                    Sm[j * H + j] = dj;
-                    for (int r = j + 1; r < H; ++r) {
-                        double v = Sm[r * H + j];
-                        for (int q = 0; q < j; ++q) v -= Sm[r * H + q] * Sm[j * H + q];
-                        Sm[r * H + j] = v / dj;
+                    Sm[j * H2 + j] = dj;
+                    for (int r = j + 1; r < H2; ++r) {
+                        double v = Sm[r * H2 + j];
+                        for (int q = 0; q < j; ++q) v -= Sm[r * H2 + q] * Sm[j * H2 + q];
+                        Sm[r * H2 + j] = v / dj;
                     }
                 }
             }
@@ -367,6 +462,9 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             double dw = 0.0, ds = 0.0, dl1 = 0.0, dl2 = 0.0, dl3 = 0.0, step = 0.0, prev_dw = 0.0;
             double rc5 = 0.0, dl5 = 0.0;
             if constexpr (BOX) rc5 = x5 * l5;
+            if constexpr (CAP) {
+                if (k < H) rc6[k] = x6[k] * l6[k];
+            }
             for (int pass = 0; pass < 2; ++pass) {
                 const double p2 = rc2 / z2 + al * rg2, p3 = rc3 / z3 + be * rg3;
                 const double qs = (act && hs) ? -rs - p2 - p3 : 0.0;
@@ -374,28 +472,43 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                 const double vn = next_period(v, vec, k, n, N);
                 double rhs = act ? -rw - (hw ? rc1 / w : 0.0) - (v - vn) : 0.0;
                 if constexpr (BOX) rhs += rc5 / x5;
+                double r3 = 0.0;   // CAP: the cap row's right-hand side of the lane's period
+                if constexpr (CAP) {
+                    period_sums(P * qs, vec, pv, k, n, N, H);
+                    if (k < H) r3 = -pv[k] + rg6[k] + rc6[k] / l6[k];
+                }
                 const double x = chol_solve(M, n, rhs, vec);
+                if constexpr (CAP) {
+                    const double xm = prev_period(x, vec, k, n, N, 0.0);
+                    period_sums(act ? -g * (x - xm) : 0.0, vec, pc, k, n, N, H);
+                    if (k < H) cx[k] = pc[k] - r3;
+                }
                 period_sums(x, vec, pv, k, n, N, H);
-                if (k == 0) {   // dnu = S^{-1} (A x + r_p)
-                    for (int j = 0; j < H; ++j) {
-                        double u = pv[j] + rpv[j];
-                        for (int q = 0; q < j; ++q) u -= Sm[j * H + q] * dnu[q];
-                        dnu[j] = u / Sm[j * H + j];
+                if (k == 0) {   // dnu = S^{-1} (A x + r_p); CAP: [dnu; dl6] = S^{-1} [A x + r_p; C x - r3]
+                    for (int j = 0; j < H2; ++j) {
+                        double u = (!CAP || j < H) ? pv[j] + rpv[j] : cx[j - H];
+                        for (int q = 0; q < j; ++q) u -= Sm[j * H2 + q] * dnu[q];
+                        dnu[j] = u / Sm[j * H2 + j];
                     }
-                    for (int j = H - 1; j >= 0; --j) {
+                    for (int j = H2 - 1; j >= 0; --j) {
                         double u = dnu[j];
-                        for (int q = j + 1; q < H; ++q) u -= Sm[q * H + j] * dnu[q];
-                        dnu[j] = u / Sm[j * H + j];
+                        for (int q = j + 1; q < H2; ++q) u -= Sm[q * H2 + j] * dnu[q];
+                        dnu[j] = u / Sm[j * H2 + j];
                     }
                 }
                 __syncthreads();
                 dw = x;
                 if (act)
-                    for (int q = 0; q < H; ++q) dw -= Y[(size_t)q * n + k] * dnu[q];
+                    for (int q = 0; q < H2; ++q) dw -= Y[(size_t)q * n + k] * dnu[q];
                 const double dwm = prev_period(dw, vec, k, n, N, 0.0);
                 prev_dw = dwm;
                 const double dd = dw - dwm;
                 ds = (act && hs) ? P * (qs - (be - al) * dd) : 0.0;
+                if constexpr (CAP) {
+                    if (act) ds -= P * dnu[H + t];
+                    period_sums(ds, vec, pv, k, n, N, H);
+                    if (k < H) dx6[k] = -pv[k] + rg6[k];
+                }
                 const double dz2 = ds - dd + rg2, dz3 = ds + dd + rg3;
                 dl1 = (act && hw) ? -(l1 * dw + rc1) / w : 0.0;
                 dl2 = (act && hs) ? -(l2 * dz2 + rc2) / z2 : 0.0;
@@ -410,12 +523,18 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                 if constexpr (BOX) {
                     if (act) { am = to_bound(x5, -dw, am); am = to_bound(l5, dl5, am); }
                 }
+                if constexpr (CAP) {
+                    if (k < H) { am = to_bound(x6[k], dx6[k], am); am = to_bound(l6[k], dnu[H + k], am); }
+                }
                 am = block_min(am, red);
                 if (pass == 1) { step = fmin(1.0, 0.99 * am); break; }
                 const double ap = fmin(1.0, am);
                 double compa = act ? (w + ap * dw) * (l1 + ap * dl1) + (z2 + ap * dz2) * (l2 + ap * dl2) +
                                          (z3 + ap * dz3) * (l3 + ap * dl3) : 0.0;
                 if constexpr (BOX) compa += (x5 - ap * dw) * (l5 + ap * dl5);
+                if constexpr (CAP) {
+                    if (k < H) compa += (x6[k] + ap * dx6[k]) * (l6[k] + ap * dnu[H + k]);
+                }
                 const double mua = block_sum(compa, red) * inv_m;
                 double sg = mua / mu_c;
                 sg = sg * sg * sg;
@@ -424,6 +543,9 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                 if (act && hs) { rc2 = z2 * l2 + dz2 * dl2 - smu; rc3 = z3 * l3 + dz3 * dl3 - smu; }
                 if constexpr (BOX) {
                     if (act) rc5 = x5 * l5 - dw * dl5 - smu;
+                }
+                if constexpr (CAP) {
+                    if (k < H) rc6[k] = x6[k] * l6[k] + dx6[k] * dnu[H + k] - smu;
                 }
             }
             w += step * dw;
@@ -438,12 +560,18 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             if constexpr (BOX) l5 += step * dl5;
             __syncthreads();
             if (k < H) nu[k] += step * dnu[k];
+            if constexpr (CAP) {
+                if (k < H) { x6[k] += step * dx6[k]; l6[k] += step * dnu[H + k]; }
+            }
             __syncthreads();
         }
         if (unbounded) status = KMPC_STATUS_UNBOUNDED;
         else if (best <= 1e-7) status = KMPC_STATUS_OPTIMAL;
         else if (best <= 1e-4) status = KMPC_STATUS_OPTIMAL_INACCURATE;
         else status = KMPC_STATUS_SOLVER_ERROR;
+        if constexpr (CAP) {
+            if (cap_iter < 0) status = KMPC_STATUS_INFEASIBLE;   // d0 > tau (capped_start)
+        }
     }
     __syncthreads();
     const bool ok = status == KMPC_STATUS_OPTIMAL || status == KMPC_STATUS_OPTIMAL_INACCURATE;
@@ -455,16 +583,16 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     }
 }
 
-template <int MAXT, bool GM, bool BOX>
+template <int MAXT, bool GM, bool BOX, bool CAP>
 __global__ void __launch_bounds__(MAXT) mv_ipm_kernel(MvArgs a) {
     extern __shared__ double lds[];
     if (GM) {
         for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-            mv_window<true, BOX>(a, b, lds);
+            mv_window<true, BOX, CAP>(a, b, lds);
             __syncthreads();
         }
     } else {
-        mv_window<false, BOX>(a, blockIdx.x, lds);
+        mv_window<false, BOX, CAP>(a, blockIdx.x, lds);
     }
 }
 
@@ -488,6 +616,7 @@ struct MvBt {
     const double* gamma;      // SWEEP: [C] device, the solve's gamma
     const double* mv_cost;    // SWEEP: [C] device, the solve's cost_coeff
     const double* bt_cost;    // SWEEP: [C] device, the bookkeeping's cost_coeff
+    const double* max_turnover;   // SWEEP of the CAP kernels: [C] device, the solve's turnover cap
     bt::StepArgs st;          // st.k = the first step's history row; st.target = the W0 rows [items, N]
 };
 
@@ -496,8 +625,9 @@ struct MvBt {
 // window 0 of a per-item copy whose pointers are the item's rows. A held step reports status
 // optimal and obj NaN. SWEEP: a config outside the program (gamma < 0, cost_coeff < 0 or a
 // non-finite value; the host cannot see the values) gets a NaN parameter, which mv_window answers
-// with KMPC_STATUS_SOLVER_ERROR and the hold fallback at every step.
-template <bool GM, bool BOX, bool SWEEP>
+// with KMPC_STATUS_SOLVER_ERROR and the hold fallback at every step; so does a cap that is not
+// finite or not > 0 (CAP kernels).
+template <bool GM, bool BOX, bool CAP, bool SWEEP>
 __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int q, double* lds, double* red) {
     const int N = a0.N, n = a0.N * a0.H;
     int p = q;
@@ -510,12 +640,15 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
         if (!(cj >= 0.0) || !isfinite(cj)) cj = __builtin_nan("");
         cb = r.bt_cost[j];
     }
+    double tj = a0.max_turnover;
+    if constexpr (SWEEP && CAP) tj = r.max_turnover[q / r.P];
     const size_t PN = (size_t)r.P * N;
     for (int k = 0; k < r.n_steps; ++k) {
         const size_t kp = (size_t)k * r.P + p;
         if (r.valid[kp]) {   // (one value per workgroup: mv_window's barriers stay uniform)
             MvArgs a = a0;
             a.gamma = gj; a.c = cj;
+            if constexpr (CAP) a.max_turnover = tj;
             a.return_full = 0;
             a.mu = r.mu + kp * n;
             a.sigma = r.sigma + kp * N * N;
@@ -524,7 +657,7 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
             a.status = a0.status + q;
             a.obj = a0.obj + q;
             a.iters = nullptr;
-            mv_window<GM, BOX>(a, 0, lds);
+            mv_window<GM, BOX, CAP>(a, 0, lds);
         } else {
             for (int i = threadIdx.x; i < N; i += blockDim.x) a0.wout[(size_t)q * N + i] = a0.wp[(size_t)q * N + i];
             if (threadIdx.x == 0) {
@@ -542,14 +675,14 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
     }
 }
 
-template <int MAXT, bool GM, bool BOX, bool SWEEP>
+template <int MAXT, bool GM, bool BOX, bool CAP, bool SWEEP>
 __global__ void __launch_bounds__(MAXT) mv_bt_kernel(MvArgs a0, MvBt r) {
     extern __shared__ double lds[];
     __shared__ double red[4];   // the bookkeeping's reduction slots (nbt <= 256: four waves)
     if (GM) {
-        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, SWEEP>(a0, r, q, lds, red);
+        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, CAP, SWEEP>(a0, r, q, lds, red);
     } else {
-        mv_bt_item<false, BOX, SWEEP>(a0, r, blockIdx.x, lds, red);
+        mv_bt_item<false, BOX, CAP, SWEEP>(a0, r, blockIdx.x, lds, red);
     }
 }
 
@@ -612,10 +745,30 @@ size_t mv_workspace_bytes(const kmpc_mv_desc* d) {
     const size_t slots = d->B < MV_SLOTS ? d->B : MV_SLOTS;
     return sizeof(double) * mv_slab(d->N, d->H) * slots;
 }
+// ... and of the CAP form: Sm [2H][2H], thirteen H-vectors (mv_window: pv, nu, dnu [2H], rpv and the
+// eight of the cap rows), Y [2H][n]. The LDS variant holds every n <= 128 (110,864 bytes at n = 128,
+// H = 16).
+size_t mv_cap_small_bytes(int N, int H) {
+    return sizeof(double) * (2 * (size_t)N * H + 4 * (size_t)H * H + 13 * (size_t)H + 18);
+}
+size_t mv_cap_lds_bytes(int N, int H) {
+    const size_t n = (size_t)N * H;
+    return mv_cap_small_bytes(N, H) + sizeof(double) * (n * (n + 1) / 2 + 2 * H * n);
+}
+static bool mv_cap_in_lds(int N, int H) { return (size_t)N * H <= 128 && mv_cap_lds_bytes(N, H) <= 160 * 1024; }
+static size_t mv_cap_slab(int N, int H) {
+    const size_t n = (size_t)N * H;
+    return n * (n + 1) / 2 + 2 * H * n;
+}
+size_t mv_cap_workspace_bytes(const kmpc_mv_desc* d) {
+    if (!d || d->B <= 0 || mv_cap_in_lds(d->N, d->H)) return 0;
+    const size_t slots = d->B < MV_SLOTS ? d->B : MV_SLOTS;
+    return sizeof(double) * mv_cap_slab(d->N, d->H) * slots;
+}
 
 int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma, size_t sigma_stride,
                     const double* w_prev, double* w_out, int* status, double* obj, int* iters,
-                    void* ws, size_t ws_bytes, hipStream_t stream, double max_weight) {
+                    void* ws, size_t ws_bytes, hipStream_t stream, double max_weight, double max_turnover) {
     MvArgs a;
     a.B = d->B; a.N = d->N; a.H = d->H;
     a.gamma = d->gamma; a.c = d->cost_coeff;
@@ -627,29 +780,50 @@ int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma
     a.wout = w_out; a.status = status; a.obj = obj; a.iters = iters;
     a.ws = (double*)ws; a.slab = mv_slab(d->N, d->H);
     a.max_weight = max_weight;
+    a.max_turnover = max_turnover;
     const bool box = max_weight > 0.0;   // kmpc_solve_mv_box (long-only, N u > 1, u < 1); else the plain kernels
     const int n = d->N * d->H;
     const int nt = 64 * ((n + 63) / 64);
-    if (mv_in_lds(d->N, d->H)) {
+    if (max_turnover > 0.0) {   // kmpc_solve_mv_cap: the CAP kernels, their own LDS and slab sizes
+        a.slab = mv_cap_slab(d->N, d->H);
+        if (mv_cap_in_lds(d->N, d->H)) {
+            const size_t lds = mv_cap_lds_bytes(d->N, d->H);
+            if (box)
+                hipLaunchKernelGGL((mv_ipm_kernel<128, false, true, true>), dim3(d->B), dim3(nt), lds, stream, a);
+            else
+                hipLaunchKernelGGL((mv_ipm_kernel<128, false, false, true>), dim3(d->B), dim3(nt), lds, stream, a);
+        } else {
+            const size_t lds = mv_cap_small_bytes(d->N, d->H);
+            if (n > 1024 || lds > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
+            if (!ws || ws_bytes < mv_cap_workspace_bytes(d)) return KMPC_ERR_WORKSPACE;
+            const int grid = d->B < MV_SLOTS ? d->B : MV_SLOTS;
+            if (box)
+                hipLaunchKernelGGL((mv_ipm_kernel<1024, true, true, true>), dim3(grid), dim3(nt), lds, stream, a);
+            else
+                hipLaunchKernelGGL((mv_ipm_kernel<1024, true, false, true>), dim3(grid), dim3(nt), lds, stream, a);
+        }
+    } else if (mv_in_lds(d->N, d->H)) {
         if (box)
-            hipLaunchKernelGGL((mv_ipm_kernel<128, false, true>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
+            hipLaunchKernelGGL((mv_ipm_kernel<128, false, true, false>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
         else
-            hipLaunchKernelGGL((mv_ipm_kernel<128, false, false>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
+            hipLaunchKernelGGL((mv_ipm_kernel<128, false, false, false>), dim3(d->B), dim3(nt), mv_lds_bytes(d->N, d->H), stream, a);
     } else {
         if (n > 1024 || mv_small_bytes(d->N, d->H) > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
         if (!ws || ws_bytes < mv_workspace_bytes(d)) return KMPC_ERR_WORKSPACE;
         const int grid = d->B < MV_SLOTS ? d->B : MV_SLOTS;
         if (box)
-            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, true>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
+            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, true, false>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
         else
-            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, false>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
+            hipLaunchKernelGGL((mv_ipm_kernel<1024, true, false, false>), dim3(grid), dim3(nt), mv_small_bytes(d->N, d->H), stream, a);
     }
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
 // kmpc_markowitz_run (n_cfg = 0) / kmpc_markowitz_sweep: the arguments are checked by the C ABI;
-// here the storage variant, the workspace and the launch.
-int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, int n_cfg,
+// here the storage variant, the workspace and the launch. cap: the CAP kernels (kmpc_markowitz_run_cap
+// / _sweep_cap), their cap max_turnover (run) or the configs' caps [n_cfg] (sweep, device).
+int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, bool cap,
+                 double max_turnover, const double* cfg_turnover, int n_cfg,
                  const double* gamma, const double* mv_cost, const double* bt_cost, int step0, int n_steps,
                  const double* mu, const double* sigma, const int* valid, const float* realized, int n_real,
                  double* weights, double* value, double* hist, double* target, int* status, double* obj,
@@ -667,35 +841,38 @@ int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max
     a.return_full = 0;
     a.mu = mu; a.sigma = sigma; a.sigma_stride = (size_t)d->N * d->N; a.wp = weights;
     a.wout = target; a.status = status; a.obj = obj; a.iters = nullptr;
-    a.ws = (double*)ws; a.slab = mv_slab(d->N, d->H);
+    a.ws = (double*)ws; a.slab = cap ? mv_cap_slab(d->N, d->H) : mv_slab(d->N, d->H);
     a.max_weight = max_weight;
+    a.max_turnover = max_turnover;
     MvBt r;
     r.P = bd->P; r.items = items; r.n_steps = n_steps; r.n_real = n_real;
     r.nbt = d->N >= 256 ? 256 : 64 * ((d->N + 63) / 64);   // (backtest_step_launch's block)
     r.mu = mu; r.sigma = sigma; r.valid = valid; r.realized = realized;
-    r.gamma = gamma; r.mv_cost = mv_cost; r.bt_cost = bt_cost;
+    r.gamma = gamma; r.mv_cost = mv_cost; r.bt_cost = bt_cost; r.max_turnover = cfg_turnover;
     r.st.P = items; r.st.N = d->N; r.st.S = bd->S; r.st.k = step0; r.st.c = sweep ? 0.0 : bd->cost_coeff;
     r.st.target = target; r.st.realized = nullptr; r.st.w = weights; r.st.value = value; r.st.hist = hist;
     const bool box = max_weight > 0.0;
     const int n = d->N * d->H;
     const int nt = 64 * ((n + 63) / 64);   // >= r.nbt
-    const bool in_lds = mv_in_lds(d->N, d->H);
+    const bool in_lds = cap ? mv_cap_in_lds(d->N, d->H) : mv_in_lds(d->N, d->H);
+    const size_t small = cap ? mv_cap_small_bytes(d->N, d->H) : mv_small_bytes(d->N, d->H);
     if (!in_lds) {
-        if (n > 1024 || mv_small_bytes(d->N, d->H) > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
-        if (!ws || ws_bytes < mv_workspace_bytes(&di)) return KMPC_ERR_WORKSPACE;
+        if (n > 1024 || small > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
+        if (!ws || ws_bytes < (cap ? mv_cap_workspace_bytes(&di) : mv_workspace_bytes(&di))) return KMPC_ERR_WORKSPACE;
     }
     const dim3 grid(in_lds ? items : (items < MV_SLOTS ? items : MV_SLOTS));
-    const size_t lds = in_lds ? mv_lds_bytes(d->N, d->H) : mv_small_bytes(d->N, d->H);
-    const auto launch = [&](auto bx, auto sw) {
+    const size_t lds = !in_lds ? small : cap ? mv_cap_lds_bytes(d->N, d->H) : mv_lds_bytes(d->N, d->H);
+    const auto launch = [&](auto bx, auto cp, auto sw) {
         if (in_lds)
-            hipLaunchKernelGGL((mv_bt_kernel<128, false, decltype(bx)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
+            hipLaunchKernelGGL((mv_bt_kernel<128, false, decltype(bx)::value, decltype(cp)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
         else
-            hipLaunchKernelGGL((mv_bt_kernel<1024, true, decltype(bx)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
+            hipLaunchKernelGGL((mv_bt_kernel<1024, true, decltype(bx)::value, decltype(cp)::value, decltype(sw)::value>), grid, dim3(nt), lds, stream, a, r);
     };
     using T = std::true_type;
     using F = std::false_type;
-    if (box) { if (sweep) launch(T{}, T{}); else launch(T{}, F{}); }
-    else     { if (sweep) launch(F{}, T{}); else launch(F{}, F{}); }
+    const auto by_cap = [&](auto bx, auto sw) { if (cap) launch(bx, T{}, sw); else launch(bx, F{}, sw); };
+    if (box) { if (sweep) by_cap(T{}, T{}); else by_cap(T{}, F{}); }
+    else     { if (sweep) by_cap(F{}, T{}); else by_cap(F{}, F{}); }
     return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 

@@ -38,6 +38,7 @@ class MPCConfig:
     precision: str = "auto"  # kmpc_solve_desc.precision: "mixed" (float32 warm-start phase + float64 finish where available), "f64", or "auto" (mixed from 2,048 windows per call, else f64)
     mu_handoff: float = 0.0  # float32 -> float64 handoff at mu <= mu_handoff (0 -> kernel default 3e-5)
     max_weight: float = 0.0  # per-asset position limit w <= max_weight of the log-utility (kmpc_solve_box) and the mean-variance (kmpc_solve_mv_box) solves; 0 or >= 1: none
+    mv_max_turnover: float = 0.0  # L1 turnover cap ||w_t - w_{t-1}||_1 <= mv_max_turnover of the mean-variance solve (kmpc_solve_mv_cap); 0: none, the reference's program (max_turnover above is the log-utility solve's and stays unread there)
 
 
 def _box_limit(config: MPCConfig, N: int) -> float:
@@ -56,6 +57,18 @@ def _box_limit(config: MPCConfig, N: int) -> float:
     if int(N) * u <= 1.0:
         raise ValueError(f"max_weight = {u} leaves no room with N = {int(N)} assets (N * max_weight must exceed 1)")
     return u
+
+
+def _mv_turnover_cap(config: MPCConfig) -> float:
+    """The active L1 turnover cap of the mean-variance solve of `config`, or 0.0 when it has none
+    (mv_max_turnover 0: the reference's program; MPCConfig.max_turnover is the log-utility solve's
+    and is not read here). kmpc_mv_desc cannot carry the cap, so every caller that turns an
+    MPCConfig into a mean-variance solve goes through here and then through kmpc_solve_mv_cap.
+    Raises ValueError on a negative or NaN cap."""
+    tau = float(getattr(config, "mv_max_turnover", 0.0))
+    if tau != tau or tau < 0.0:
+        raise ValueError(f"mv_max_turnover must be >= 0 (got {tau})")
+    return tau
 
 
 def _solve_desc(B: int, N: int, H: int, config: MPCConfig, full: bool) -> _lib.SolveDesc:
@@ -238,7 +251,7 @@ def solve_mpc_mean_variance_batched(
     with_iters: bool = False,
 ):
     """Batched mean-variance solve on the device (kmpc_solve_mv_ws; kmpc_solve_mv_box with a
-    position limit).
+    position limit; kmpc_solve_mv_cap with a turnover cap).
 
     Args:
         current_weights: [B, N] device tensor (float64; other dtypes are converted).
@@ -247,7 +260,9 @@ def solve_mpc_mean_variance_batched(
         cov_matrix: [B, N, N] per-window covariance, or one shared [N, N] (mpc.py:123).
         config: MPCConfig (gamma, cost_coeff, allow_short, and max_weight: the per-asset position
             limit w <= max_weight, long-only, N * max_weight > 1 — ValueError otherwise; 0 or >= 1:
-            none; max_turnover is not part of this program in the reference either).
+            none; max_turnover is not part of this program in the reference either;
+            mv_max_turnover: the L1 turnover cap of every period, 0: none — a window whose w_prev
+            lies further than the cap from the feasible set reports "infeasible" and the fallback).
         return_full: return W [B, H, N] instead of W[:, 0].
 
     Returns:
@@ -282,11 +297,16 @@ def solve_mpc_mean_variance_batched(
     d = _mv_desc(B, N, H, config, return_full)
     L = _lib.load()
     u = _box_limit(config, N)
+    tau = _mv_turnover_cap(config)
     with torch.cuda.device(dev):
-        nws = int(L.kmpc_mv_workspace_bytes(ctypes.byref(d)))
+        nws = int((L.kmpc_mv_cap_workspace_bytes if tau else L.kmpc_mv_workspace_bytes)(ctypes.byref(d)))
         ws = _workspace(dev, nws) if nws else None
-        # (the position limit: the BOX form of the same kernels, same workspace)
-        entry, head = (L.kmpc_solve_mv_box, (ctypes.byref(d), u)) if u else (L.kmpc_solve_mv_ws, (ctypes.byref(d),))
+        # (the position limit: the BOX form of the same kernels, same workspace; the turnover cap:
+        # their CAP form, with or without the limit, and its larger workspace)
+        if tau:
+            entry, head = L.kmpc_solve_mv_cap, (ctypes.byref(d), u, tau)
+        else:
+            entry, head = (L.kmpc_solve_mv_box, (ctypes.byref(d), u)) if u else (L.kmpc_solve_mv_ws, (ctypes.byref(d),))
         rc = entry(*head, mu64.data_ptr(), S.data_ptr(), stride, wp.data_ptr(),
                    W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
                    ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
