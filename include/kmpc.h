@@ -582,6 +582,58 @@ int kmpc_markowitz_sweep_cap(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc
                              int n_real, double* weights, double* value, double* hist, double* target, int* status,
                              double* obj, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- mean-variance MPC, band form: the multi-period solve for a forecast sequence (added within
+ * ABI 0.7.0, see the version note at the end). The program is kmpc_solve_mv_cap's (mean-variance,
+ * optional position limit, optional turnover cap) with mu_t = yhat_t, the rollout's float32 forecast
+ * [B,H,N] exactly as kmpc_rollout writes it (widened to float64 in the kernel, which is exact; no
+ * float64 copy). The Newton matrix M = 2 gamma (I_H (x) Sigma) + diag + D' diag(E) D is block
+ * tridiagonal with diagonal off-diagonal blocks: half-bandwidth N, and its Cholesky factor has no fill
+ * outside the band. These kernels keep N + 1 doubles per row of M (columns r - N .. r) and clip the
+ * factorization and the triangular solves to the band; the interior point around them, the statuses
+ * (KMPC_STATUS_INFEASIBLE for d0 > max_turnover, SOLVER_ERROR for non-finite input, UNBOUNDED) and the
+ * fallback (tile(w_prev), obj NaN) are those of the dense kernels, which every other kmpc_solve_mv*
+ * and kmpc_markowitz_* entry keeps using. On the same (float32-representable) mu a window ends with
+ * the dense kernel's status and optimum. At H = 1 the band is the full triangle.
+ * Storage: a window's M and Y sit in LDS while the window's LDS footprint is at most
+ * KMPC_MV_BAND_LDS_BYTES (e.g. N = 10, H = 5; N = 30, H = 5; N = 61, H = 2 without the cap); past that
+ * in a slab of the workspace, n (N + 1) + SH H n doubles per window in flight (n = H*N; SH = 1, or 2
+ * with the cap; at most 512 windows in flight): kmpc_mv_band_workspace_bytes(desc, with_cap), 0 in the
+ * LDS case. with_cap != 0: the size for a call with max_turnover > 0.
+ *   sigma_per_window: 0: one shared Sigma [N,N]; otherwise Sigma [B,N,N].
+ *   max_weight:   0: no limit. Otherwise the rules of kmpc_solve_mv_box in its order (NaN or < 0
+ *                 KMPC_ERR_INVALID, allow_short KMPC_ERR_UNSUPPORTED, >= 1 an inactive bound,
+ *                 N * max_weight <= 1 KMPC_ERR_INVALID).
+ *   max_turnover: 0: no cap. NaN or < 0: KMPC_ERR_INVALID.
+ * Return codes, all decided before any launch (and before the B == 0 return), in this order: desc as
+ * kmpc_solve_mv_ws (KMPC_ERR_INVALID; KMPC_ERR_UNSUPPORTED past H <= KMPC_MV_MAX_H,
+ * H*N <= KMPC_MV_MAX_HN); max_turnover; max_weight; B == 0 returns KMPC_OK; null arrays (iters may be
+ * NULL) KMPC_ERR_INVALID; KMPC_ERR_WORKSPACE without kmpc_mv_band_workspace_bytes bytes. */
+#define KMPC_MV_BAND_LDS_BYTES 65536
+size_t kmpc_mv_band_workspace_bytes(const kmpc_mv_desc* desc, int with_cap);
+int kmpc_solve_mv_band(const kmpc_mv_desc* desc, const float* yhat /* [B,H,N] f32 */, const double* sigma,
+                       int sigma_per_window, const double* w_prev, double max_weight, double max_turnover,
+                       double* w_out, int* status, double* obj, int* iters, void* workspace, size_t ws_bytes,
+                       void* stream);
+
+/* The mean-variance Koopman-MPC backtest for P paths in ONE launch (added within ABI 0.7.0): steps
+ * step0 .. step0 + n_steps - 1 of every path, each the window of kmpc_solve_mv_band — that step's
+ * forecast yhat and covariance, from the path's current (drifted) weights — where valid, else the
+ * hold, then the kmpc_backtest_step bookkeeping, one workgroup per path. A step whose window does not
+ * end optimal (infeasible under limit and cap, non-finite input) holds and the path goes on. The
+ * results are bit-identical to the per-step loop of kmpc_solve_mv_band and kmpc_backtest_step: the
+ * same window body and the same bookkeeping sums.
+ *   yhat [n_steps, P, H, N] f32, sigma [n_steps, P, N, N] f64, valid [n_steps, P] int.
+ *   max_weight, max_turnover: as kmpc_solve_mv_band.
+ *   workspace: kmpc_mv_band_workspace_bytes of mvdesc with B = P.
+ * Every other array and rule — bdesc, mvdesc (B ignored, return_full_W = 0), realized, n_real, weights,
+ * value, hist, target, status, obj, chunking through step0, the n_steps = 0 shape probe and the P = 0
+ * return — as kmpc_markowitz_run_cap. */
+int kmpc_koopman_mv_run(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, double max_weight,
+                        double max_turnover, int step0, int n_steps, const float* yhat, const double* sigma,
+                        const int* valid, const float* realized, int n_real, double* weights, double* value,
+                        double* hist, double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                        void* stream);
+
 /* Workspace needed by kmpc_rollout / kmpc_solve / kmpc_window (either desc may be NULL; with both,
    the sum for kmpc_window: rollout scratch + yhat + the solve's). */
 size_t kmpc_workspace_bytes(const kmpc_rollout_desc* rdesc, const kmpc_solve_desc* sdesc);
@@ -610,7 +662,10 @@ const char* kmpc_strerror(int code);
    code it had).
    kmpc_mv_cap_workspace_bytes, kmpc_solve_mv_cap, kmpc_markowitz_run_cap and kmpc_markowitz_sweep_cap
    were added within 0.7.0 in the same way: four new functions, no struct, enum or existing function
-   changed. */
+   changed.
+   kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run were added within 0.7.0 in
+   the same way: three new functions (and the constant KMPC_MV_BAND_LDS_BYTES), no struct, enum or
+   existing function changed. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

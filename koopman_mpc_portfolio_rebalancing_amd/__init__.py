@@ -6,11 +6,13 @@ Drop-in for the reference's per-window hot path (yli421/koopman-mpc-portfolio-re
 (backtest.py), executed by hand-written gfx950 kernels in libkmpc.so (C ABI: include/kmpc.h).
 """
 from .mpc import (MPCConfig, gross_returns, log_utility_value_batched, solve_mpc_log_utility,  # noqa: F401
-                  solve_mpc_log_utility_batched, solve_mpc_mean_variance, solve_mpc_mean_variance_batched)
+                  solve_mpc_log_utility_batched, solve_mpc_mean_variance, solve_mpc_mean_variance_banded,
+                  solve_mpc_mean_variance_banded_batched, solve_mpc_mean_variance_batched)
 from .koopman import DeviceKoopman, KoopmanModelSpec, standardize_panel  # noqa: F401
 from .backtest import (BacktestConfig, BuyAndHoldStrategy, KoopmanMPCStrategy, Strategy,  # noqa: F401
                        calculate_metrics, run_backtest, run_backtest_lockstep, run_backtest_sweep,
                        sweep_backtest)
-from .baselines import run_markowitz_lockstep, run_markowitz_sweep, sweep_backtest_markowitz  # noqa: F401
+from .baselines import (KoopmanMVStrategy, run_koopman_mv_lockstep, run_markowitz_lockstep,  # noqa: F401
+                        run_markowitz_sweep, sweep_backtest_markowitz)
 
 __version__ = "0.7.0"

@@ -27,10 +27,11 @@ import pandas as pd
 import torch
 
 from . import _lib
-from .backtest import (METRIC_NAMES, BacktestConfig, KoopmanMPCStrategy, Strategy, _cache_hit, _cache_key,
-                       _env_stats, run_backtest)
+from .backtest import (METRIC_NAMES, PREROLL_CHUNK, BacktestConfig, KoopmanMPCStrategy, Strategy, _cache_hit,
+                       _cache_key, _env_stats, _prepare_paths, run_backtest)
 from .koopman import KoopmanModelSpec
-from .mpc import MPCConfig, _box_limit, _mv_desc, _mv_turnover_cap, _workspace, solve_mpc_mean_variance_batched
+from .mpc import (MPCConfig, _box_limit, _mv_band_program, _mv_desc, _mv_turnover_cap, _workspace,
+                  solve_mpc_mean_variance_banded_batched, solve_mpc_mean_variance_batched)
 
 
 def fit_dmd(train_data) -> np.ndarray:
@@ -461,6 +462,152 @@ def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Seque
     return [pd.DataFrame({"date": dates, **{k: v[j] for k, v in cols.items()}}) for j in range(len(strats))]
 
 
+# ---- mean-variance Koopman-MPC: the forecast sequence in the mean-variance program ---------------
+
+class KoopmanMVStrategy(KoopmanMPCStrategy):
+    """The risk-aware form of KoopmanMPCStrategy: the multi-period mean-variance program
+    (mpc.py:119-184) with mu_t = yhat_t, the forecast sequence of the same rollout as
+    KoopmanMPCStrategy, and Sigma the rolling covariance MarkowitzStrategy uses (the last
+    ``lookback_window`` de-standardized rows, np.cov + 1e-6 I; fewer than 5 past rows: hold), solved
+    by the band kernels (kmpc_solve_mv_band). ``rebalance`` returns W[0].
+
+    Args:
+        model: whatever KoopmanMPCStrategy accepts; ``dmd_model_spec(fit_dmd(train))`` gives the DMD
+            variant.
+        mpc_config: MPCConfig — horizon, gamma, cost_coeff, allow_short, max_weight and
+            mv_max_turnover are read (max_turnover is the log-utility solve's and is not).
+        device: as KoopmanMPCStrategy.
+    A run_backtest(strategy, env, config) drives it as any Strategy; run_koopman_mv_lockstep runs P
+    such backtests on the device.
+    """
+
+    def __init__(self, model: Any, mpc_config: MPCConfig, device: str = "cpu"):
+        super().__init__(model, mpc_config, device)
+        self._ret_cache = (None, None)
+
+    def _returns(self, env):
+        """(rows [T, >= N] float32 on the device, mean, std): what the rolling covariance reads, as
+        MarkowitzStrategy._returns."""
+        data = env.test_dataset.data
+        if not _cache_hit(self._ret_cache[0], data):
+            st = _env_stats(env)
+            if st is not None:
+                entry = (self._test_data(env), st[0], st[1])
+            else:
+                r = env.destandardize_returns(env.extract_current_returns(torch.as_tensor(data)))
+                entry = (torch.as_tensor(r).to(self._device(), torch.float32).contiguous(), None, None)
+            self._ret_cache = (_cache_key(data), entry)
+        return self._ret_cache[1]
+
+    def rebalance_batch(self, ts: Sequence[int], current_weights, env, lookback_window: int = 60,
+                        return_info: bool = False):
+        """Independent windows t in ts with their own current weights [B, N] -> W[0] [B, N] float64."""
+        N, H = int(env.n_assets), int(self.mpc_config.horizon)
+        _mv_band_program(self.mpc_config, N, H)   # (config errors before any device work)
+        km = self.device_model()
+        data = self._test_data(env)
+        obs = data.index_select(0, torch.as_tensor(np.asarray(ts, np.int64), device=km.device))
+        wp = torch.as_tensor(np.asarray(current_weights, np.float64), device=km.device).reshape(len(ts), N)
+        st = _env_stats(env)
+        if st is not None:
+            yhat = km.rollout(obs, st[0], st[1], H, N)
+        else:   # (custom de-standardisation: as KoopmanMPCStrategy.rebalance_batch)
+            y_std = km.rollout(obs, np.zeros(N), np.ones(N), H, N)
+            yhat = torch.as_tensor(env.destandardize_returns(y_std), device=km.device, dtype=torch.float32)
+        z, mean, std = self._returns(env)
+        _, sigma, valid = rolling_moments(z, ts, lookback_window, N, mean, std)
+        W0, status, value = solve_mpc_mean_variance_banded_batched(wp, yhat, sigma, self.mpc_config)
+        W0 = torch.where((valid == 0).unsqueeze(1), wp, W0)   # fewer than 5 past rows: hold
+        W0 = W0.cpu().numpy()
+        if return_info:
+            return W0, status.cpu().numpy(), value.cpu().numpy(), valid.cpu().numpy()
+        return W0
+
+    def rebalance(self, t, current_weights, env, lookback_window: int = 60) -> np.ndarray:
+        W0 = self.rebalance_batch([t], np.asarray(current_weights, np.float64).reshape(1, -1), env, lookback_window)
+        return W0[0]
+
+
+def run_koopman_mv_lockstep(strategy: "KoopmanMVStrategy", obs, realized, config: BacktestConfig, mean, std,
+                            lookback_window: int = 60, n_rows: Optional[int] = None,
+                            persistent: Optional[bool] = None) -> Dict[str, Any]:
+    """P independent backtests of KoopmanMVStrategy on the device: path p reproduces
+    run_backtest(strategy, env, config) on an env whose test rows are obs[p] and whose de-standardized
+    realized log-returns are realized[p]. Arguments as run_backtest_lockstep (obs [P, T, obs_size],
+    its first N columns the current returns; realized [P, T, N]; mean, std [N]) with the covariance's
+    lookback_window; the returned dict as run_markowitz_lockstep.
+
+    The steps go in chunks: one rollout of the chunk's windows (as the log-utility lock-step
+    pre-rolls them), one kmpc_rolling_moments_paths for its covariances (within MARKOWITZ_SIGMA_BYTES),
+    then one kmpc_koopman_mv_run — every step of a path, solve or hold then bookkeeping, in one
+    workgroup — and kmpc_backtest_metrics at the end. persistent=False runs the per-step loop of
+    kmpc_solve_mv_band, the hold select and kmpc_backtest_step instead; the two are bit-identical.
+    Config and shape errors raise ValueError before any device work."""
+    x, r = torch.as_tensor(obs), torch.as_tensor(realized)
+    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2] or x.shape[2] < r.shape[2]:
+        raise ValueError("obs must be [P, T, >= N] and realized [P, T, N]")
+    P, T, N = (int(v) for v in r.shape)
+    cfg = strategy.mpc_config
+    H = int(cfg.horizon)
+    u, tau = _mv_band_program(cfg, N, H)
+    if len(np.atleast_1d(np.asarray(mean))) < N or len(np.atleast_1d(np.asarray(std))) < N:
+        raise ValueError(f"mean and std must have {N} entries")
+    km = strategy.device_model()
+    pp = _prepare_paths(km, x, r, config, mean, std, n_rows)
+    S, dev = pp.S, km.device
+    z = pp.x.contiguous()
+    ts32 = pp.steps_t.to(torch.int32)
+    f64 = dict(dtype=torch.float64, device=dev)
+    w = torch.full((P, N), 1.0 / N, **f64)       # backtest.py:161
+    value = torch.full((P,), float(config.initial_capital), **f64)
+    hist = torch.empty((P, max(S, 1), 4), **f64)
+    metrics = torch.empty((P, 5), **f64)
+    L = _lib.load()
+    bd = _lib.BacktestDesc(P, N, max(S, 1), float(config.cost_coeff))
+    md = _mv_desc(P, N, H, cfg, False)
+    with torch.cuda.device(dev):
+        sh = _lib.stream_handle(dev)
+        if persistent is None or persistent:
+            _lib.check(L.kmpc_koopman_mv_run(ctypes.byref(bd), ctypes.byref(md), u, tau, 0, 0, None, None, None, None, 0,
+                                             None, None, None, None, None, None, None, 0, sh))   # (shape check only)
+            persistent = True
+        if P and S:
+            target = torch.empty((P, N), **f64)
+            status = torch.zeros((P,), dtype=torch.int32, device=dev)
+            objv = torch.empty((P,), **f64)
+            nws = int(L.kmpc_mv_band_workspace_bytes(ctypes.byref(md), int(bool(tau)))) if persistent else 0
+            ws = _workspace(dev, nws) if nws else None
+            sc = max(1, min(_markowitz_chunk(P, N), PREROLL_CHUNK // P))
+            for k0 in range(0, S, sc):
+                n = min(sc, S - k0)
+                y = km.rollout(pp.xt[pp.steps_t[k0:k0 + n]].reshape(n * P, -1), pp.m, pp.sd, H, N).contiguous()
+                mu = torch.empty((n, P, N), **f64)   # (the rolling mean: not read, mu is the forecast)
+                sigma = torch.empty((n, P, N, N), **f64)
+                valid = torch.empty((n, P), dtype=torch.int32, device=dev)
+                _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback_window), z.data_ptr(), int(z.shape[2]),
+                                                        pp.m.data_ptr(), pp.sd.data_ptr(), ts32[k0:k0 + n].data_ptr(),
+                                                        mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), sh))
+                tn = pp.steps_t[k0:k0 + n] + 1
+                n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
+                rr = pp.rt[tn[:n_real]].contiguous() if n_real else None
+                if persistent:
+                    _lib.check(L.kmpc_koopman_mv_run(
+                        ctypes.byref(bd), ctypes.byref(md), u, tau, k0, n, y.data_ptr(), sigma.data_ptr(),
+                        valid.data_ptr(), rr.data_ptr() if rr is not None else None, n_real, w.data_ptr(),
+                        value.data_ptr(), hist.data_ptr(), target.data_ptr(), status.data_ptr(), objv.data_ptr(),
+                        ws.data_ptr() if ws is not None else None, nws, sh))
+                    continue
+                y = y.reshape(n, P, H, N)
+                for k in range(n):
+                    W0, _, _ = solve_mpc_mean_variance_banded_batched(w, y[k], sigma[k], cfg)
+                    W0 = torch.where((valid[k] == 0).unsqueeze(1), w, W0)   # hold
+                    _lib.check(L.kmpc_backtest_step(ctypes.byref(bd), k0 + k, W0.data_ptr(),
+                                                    rr[k].data_ptr() if k < n_real else None, w.data_ptr(),
+                                                    value.data_ptr(), hist.data_ptr(), sh))
+            _lib.check(L.kmpc_backtest_metrics(ctypes.byref(bd), hist.data_ptr(), metrics.data_ptr(), sh))
+    return _markowitz_out(hist, w, metrics, S, (P,))
+
+
 __all__: Sequence[str] = ("DMDStrategy", "MarkowitzStrategy", "fit_dmd", "dmd_model_spec",
                           "rolling_moments", "Strategy", "run_markowitz_lockstep", "run_markowitz_sweep",
-                          "sweep_backtest_markowitz")
+                          "sweep_backtest_markowitz", "KoopmanMVStrategy", "run_koopman_mv_lockstep")

@@ -360,6 +360,57 @@ int kmpc_solve_mv_cap(const kmpc_mv_desc* desc, double max_weight, double max_tu
                                  ws_bytes, (hipStream_t)stream, u, max_turnover);
 }
 
+size_t kmpc_mv_band_workspace_bytes(const kmpc_mv_desc* desc, int with_cap) {
+    if (!desc || desc->N < 1 || desc->H < 1 || desc->H > KMPC_MV_MAX_H || (long long)desc->N * desc->H > KMPC_MV_MAX_HN)
+        return 0;
+    return kmpc::mv_band_workspace_bytes(desc, with_cap != 0);
+}
+
+int kmpc_solve_mv_band(const kmpc_mv_desc* desc, const float* yhat, const double* sigma, int sigma_per_window,
+                       const double* w_prev, double max_weight, double max_turnover, double* w_out, int* status,
+                       double* obj, int* iters, void* workspace, size_t ws_bytes, void* stream) {
+    // every rule is decided before any launch (and before the B == 0 return): the descriptor as
+    // kmpc_solve_mv_ws, the cap, then the limit (0: none) in mv_box_limit's order
+    if (!desc || desc->B < 0 || desc->N < 1 || desc->H < 1) return KMPC_ERR_INVALID;
+    if (desc->H > KMPC_MV_MAX_H || (long long)desc->N * desc->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (!(max_turnover >= 0.0)) return KMPC_ERR_INVALID;                // (NaN too)
+    double u = 0.0;
+    if (max_weight != 0.0) {   // (0: none, and then allow_short is allowed)
+        const int rc = mv_box_limit(*desc, max_weight, u);
+        if (rc) return rc;
+    }
+    if (desc->B == 0) return KMPC_OK;
+    if (!yhat || !sigma || !w_prev || !w_out || !status || !obj) return KMPC_ERR_INVALID;
+    return kmpc::mv_band_launch(nullptr, desc, u, max_turnover, yhat, sigma,
+                                sigma_per_window ? (size_t)desc->N * desc->N : 0, w_prev, w_out, status, obj, iters,
+                                0, 0, nullptr, nullptr, 0, nullptr, nullptr, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+int kmpc_koopman_mv_run(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, double max_turnover,
+                        int step0, int n_steps, const float* yhat, const double* sigma, const int* valid,
+                        const float* realized, int n_real, double* weights, double* value, double* hist,
+                        double* target, int* status, double* obj, void* workspace, size_t ws_bytes, void* stream) {
+    // the rules of kmpc_markowitz_run_cap in its order, all before any launch
+    if (!bd || !d || bd->P < 0 || bd->N < 1 || bd->S < 1 || step0 < 0 || n_steps < 0 ||
+        step0 + n_steps > bd->S || n_real < 0 || n_real > n_steps || d->N != bd->N || d->H < 1 ||
+        d->return_full_W)
+        return KMPC_ERR_INVALID;
+    if (d->H > KMPC_MV_MAX_H || (long long)d->N * d->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (!(max_turnover >= 0.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    double u = 0.0;   // the active limit (0: none)
+    if (max_weight != 0.0) {
+        const int rc = mv_box_limit(*d, max_weight, u);
+        if (rc) return rc;
+    }
+    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
+    if (!yhat || !sigma || !valid || !weights || !value || !hist || !target || !status || !obj ||
+        (n_real > 0 && !realized))
+        return KMPC_ERR_INVALID;
+    return kmpc::mv_band_launch(bd, d, u, max_turnover, yhat, sigma, (size_t)d->N * d->N, weights, target, status,
+                                obj, nullptr, step0, n_steps, valid, realized, n_real, value, hist, workspace,
+                                ws_bytes, (hipStream_t)stream);
+}
+
 int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int ldz,
                          const float* mean, const float* std, const int* ts,
                          double* mu, double* sigma, int* valid, void* stream) {

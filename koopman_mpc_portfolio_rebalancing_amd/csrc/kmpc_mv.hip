@@ -18,6 +18,11 @@
 // Storage: M (n x n) and M^{-1} A' sit in LDS while they fit (n <= 128); past that in a per-block
 // slab of the caller's workspace (L2-resident: 2 MB at n = 500), with a persistent grid of
 // min(B, MV_SLOTS) blocks walking the windows.
+// Band form (kmpc_solve_mv_band, kmpc_koopman_mv_run; the BAND flag of mv_window): M is block
+// tridiagonal with diagonal off-diagonal blocks, so its half-bandwidth is N and its Cholesky factor
+// has no fill outside the band. Row r keeps columns r - N .. r (N + 1 doubles), the factorization and
+// the solves are the dense ones with every loop clipped to the band, and mu is the rollout's float32
+// yhat, widened on read. Everything else of the window is the dense form's.
 //
 // Status / fallback as mpc.py:180-181: non-optimal -> W = tile(w_prev), obj = NaN.
 #include <hip/hip_runtime.h>
@@ -37,7 +42,10 @@ struct MvArgs {
     double gamma, c;
     int allow_short, max_iter, return_full;
     double tol;
-    const double* mu;       // [B, H, N]
+    union {                 // (one slot: the dense kernels' argument block keeps its layout)
+        const double* mu;   // [B, H, N]
+        const float* muf;   // BAND kernels: [B, H, N] float32 (the rollout's yhat), read in place of mu
+    };
     const double* sigma;    // [B, N, N], or one [N, N] when sigma_stride == 0
     size_t sigma_stride;    // elements between consecutive windows' Sigma
     const double* wp;       // [B, N]
@@ -149,6 +157,36 @@ __device__ double chol_solve(const double* M, int n, double b, double* vec) {
     return out;
 }
 
+// Band storage of M and its factor L: row r keeps columns r - N .. r, N + 1 doubles at pitch cs + 1,
+// column c at offset c - (r - N): entry (r, c) at r cs + N + c. cs is the distance between the rows of
+// one column, which is what the lanes of a wave stride by: N in the workspace slab (rows packed,
+// n (N + 1) doubles), N | 1 in LDS (odd, so an even N does not fold a column onto a few banks; one
+// pad double per row then). Rows r < N leave their first N - r slots unused. bnd(r, 0) is the row's
+// base for indexing by column.
+__device__ __forceinline__ size_t bnd(int r, int c, int N, int cs) { return (size_t)r * cs + (size_t)(N + c); }
+
+// chol_solve on the band factor: row r reads L[r, r - N .. r - 1] going forward and L[r + 1 .. r + N, r]
+// going back; the entries it skips are the zeros the dense form multiplies by.
+__device__ double chol_solve_band(const double* M, int n, int N, int bcs, double b, double* vec) {
+    const int r = threadIdx.x;
+    double x = b;
+    for (int j = 0; j < n; ++j) {
+        if (r == j) vec[j] = x / M[bnd(j, j, N, bcs)];
+        __syncthreads();
+        if (r > j && r < n && r <= j + N) x -= M[bnd(r, j, N, bcs)] * vec[j];
+    }
+    double y = r < n ? vec[r] : 0.0;
+    __syncthreads();
+    for (int j = n - 1; j >= 0; --j) {
+        if (r == j) vec[j] = y / M[bnd(j, j, N, bcs)];
+        __syncthreads();
+        if (r < j && r >= j - N) y -= M[bnd(j, r, N, bcs)] * vec[j];
+    }
+    const double out = r < n ? vec[r] : 0.0;
+    __syncthreads();
+    return out;
+}
+
 // CAP kernels: feasibility of period 0 and the start point; returns the iteration bound. p is w_prev clipped
 // to the bounds, out = ||p - w_prev||_1 and d0 = out + |1 - 1'p| the L1 distance from w_prev to the
 // feasible set: d0 > tau has no feasible point (-1: infeasible), and a tau outside the program (not
@@ -187,7 +225,12 @@ __device__ __forceinline__ int capped_start(const MvArgs& a, double wpi, bool ac
 // The statements the CAP = false forms run are left word for word as they were and the CAP form
 // overrides them under if constexpr (the start's s, z2, z3; the loop bound): even a local for 1 / N
 // changed which of two products the compiler fuses there, and with it the uncapped results' last bits.
-template <bool GM, bool BOX, bool CAP>
+// BAND: M and L in the band layout (bnd), n (N + 1) doubles; the assembly of M, the factorization and
+// chol_solve clipped to the band; mu read from a.muf (float32). Orthogonal to BOX (M's diagonal only)
+// and CAP (columns of Y, rows of the Schur system). The BAND = false forms keep their statements, as
+// above; the factorization's skipped terms are exact zeros there, so on the same mu the band form
+// repeats the dense form's arithmetic.
+template <bool GM, bool BOX, bool CAP, bool BAND = false>
 __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     const int N = a.N, H = a.H, n = N * H;
     constexpr int SH = CAP ? 2 : 1, XH = CAP ? 13 : 4;   // Schur rows per period; H-vectors after Sm
@@ -196,7 +239,8 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     double* Sm = vec + n;                   // [H2][H2] the Schur complement, then its Cholesky factor
     double* idg = Sm + H2 * H2 + XH * H + 18;  // [n] 1 / L_jj of the Cholesky factor
     double* M = GM ? a.ws + (size_t)blockIdx.x * a.slab : idg + n;   // packed lower: M, then L
-    double* Y = M + tri(n, 0);              // [H2][n] M^{-1} A' (CAP: M^{-1} [A' C'])
+    const int bcs = GM ? N : (N | 1);       // BAND: the rows of a column are bcs doubles apart (bnd)
+    double* Y = M + (BAND ? (size_t)n * (bcs + 1) : tri(n, 0));   // [H2][n] M^{-1} A' (CAP: M^{-1} [A' C'])
     double* pv = Sm + H2 * H2;              // [H] period sums (after Sm in LDS, both variants)
     double* nu = pv + H;                    // [H] budget multipliers
     double* dnu = nu + H;                   // [H2] (CAP: dl6 after dnu)
@@ -222,7 +266,10 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
     const double* muv = a.mu + (size_t)b * n;
     const bool hw = !a.allow_short, hs = a.c > 0.0 || CAP;
     const double wpi = act ? wpv[i] : 0.0;
-    const double mk = act ? muv[k] : 0.0;
+    double mk_;
+    if constexpr (BAND) mk_ = act ? (double)a.muf[(size_t)b * n + k] : 0.0;   // (float32 -> float64: exact)
+    else mk_ = act ? muv[k] : 0.0;
+    const double mk = mk_;
     double* wout = a.wout + (size_t)b * (a.return_full ? n : N);
     const int nout = a.return_full ? n : N;
 
@@ -356,6 +403,18 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             const double P = (act && hs) ? 1.0 / (al + be) : 0.0;
             const double E = 4.0 * al * be * P;
             const double En = next_period(E, vec, k, n, N);
+            if constexpr (BAND) {
+                if (act) {   // column k, rows k .. k + N (the band's)
+                    const int le = k + N < n - 1 ? k + N : n - 1;
+                    for (int l = k; l <= le; ++l) {
+                        const int tl = l / N, j = l - tl * N;
+                        double v = (tl == t) ? g2 * Sig[(size_t)j * N + i] : 0.0;
+                        if (l == k) v += W1 + E + En;
+                        if (l == k + N) v -= En;
+                        M[bnd(l, k, N, bcs)] = v;
+                    }
+                }
+            } else
             if (act) {   // column k, rows l >= k (M symmetric): lanes write consecutive entries
                 for (int l = k; l < n; ++l) {
                     const int tl = l / N, j = l - tl * N;
@@ -372,6 +431,51 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
             // trailing matrix at once, M[k][c] -= L[k][panel] . L[c][panel] with row k's panel in
             // registers — one read-modify-write per entry per panel instead of per column
             constexpr int PB = 8;
+            if constexpr (BAND) {
+                // the same, clipped to the band: column j reaches rows j + 1 .. j + N, row k's update
+                // columns >= k - N; a panel's trailing update the N rows under it
+                for (int jb = 0; jb < n; jb += PB) {
+                    const int je = jb + PB < n ? jb + PB : n;
+                    for (int j = jb; j < je; ++j) {
+                        if (k == j) {
+                            const double dj = M[bnd(j, j, N, bcs)];
+                            if (!(dj > 0.0) || !(dj < 1e300)) *flag = 1;
+                            const double lj = sqrt(fmax(dj, 1e-300));
+                            M[bnd(j, j, N, bcs)] = lj;
+                            idg[j] = 1.0 / lj;
+                        }
+                        __syncthreads();
+                        const bool below = k > j && k < n && k <= j + N;   // (one value for both halves)
+                        if (below) M[bnd(k, j, N, bcs)] *= idg[j];
+                        __syncthreads();   // column j of L complete before any row reads it
+                        if (below) {
+                            double* mr = M + bnd(k, 0, N, bcs);
+                            const double lkj = mr[j];
+                            int qe = k < je - 1 ? k : je - 1;   // the panel's columns in row k ...
+                            if (qe > j + N) qe = j + N;         // ... whose rows column j reaches
+                            for (int q = j + 1; q <= qe; ++q) mr[q] = fma(-lkj, M[bnd(q, j, N, bcs)], mr[q]);
+                        }
+                    }
+                    __syncthreads();
+                    if (k >= je && k < n && k - N < je) {
+                        double* mr = M + bnd(k, 0, N, bcs);
+                        double lk[PB];
+#pragma unroll
+                        for (int p = 0; p < PB; ++p) lk[p] = (jb + p < je && jb + p >= k - N) ? mr[jb + p] : 0.0;
+                        for (int c = je; c <= k; ++c) {
+                            const double* mc = M + bnd(c, jb, N, bcs);
+                            double lc[PB];
+#pragma unroll
+                            for (int p = 0; p < PB; ++p) lc[p] = (jb + p < je && jb + p >= c - N) ? mc[p] : 0.0;
+                            double v = mr[c];
+#pragma unroll
+                            for (int p = 0; p < PB; ++p) v = fma(-lk[p], lc[p], v);
+                            mr[c] = v;
+                        }
+                    }
+                    __syncthreads();
+                }
+            } else
             for (int jb = 0; jb < n; jb += PB) {
                 const int je = jb + PB < n ? jb + PB : n;
                 for (int j = jb; j < je; ++j) {
@@ -427,7 +531,9 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                 if constexpr (CAP) {
                     if (q >= H) bq = act ? (t + 1 == q - H ? gn : 0.0) - (t == q - H ? g : 0.0) : 0.0;
                 }
-                const double yq = chol_solve(M, n, bq, vec);
+                double yq;
+                if constexpr (BAND) yq = chol_solve_band(M, n, N, bcs, bq, vec);
+                else yq = chol_solve(M, n, bq, vec);
                 if (act) Y[(size_t)q * n + k] = yq;
                 period_sums(yq, vec, pv, k, n, N, H);
                 if (k < H) Sm[k * H2 + q] = pv[k];
@@ -477,7 +583,9 @@ __device__ __forceinline__ void mv_window(const MvArgs& a, int b, double* lds) {
                     period_sums(P * qs, vec, pv, k, n, N, H);
                     if (k < H) r3 = -pv[k] + rg6[k] + rc6[k] / l6[k];
                 }
-                const double x = chol_solve(M, n, rhs, vec);
+                double x;
+                if constexpr (BAND) x = chol_solve_band(M, n, N, bcs, rhs, vec);
+                else x = chol_solve(M, n, rhs, vec);
                 if constexpr (CAP) {
                     const double xm = prev_period(x, vec, k, n, N, 0.0);
                     period_sums(act ? -g * (x - xm) : 0.0, vec, pc, k, n, N, H);
@@ -609,7 +717,10 @@ struct MvBt {
     int n_steps;              // steps run by this launch
     int n_real;               // steps k < n_real have a realized row (later ones: no market move)
     int nbt;                  // threads of the bookkeeping: bt_step_kernel's block size for this N
-    const double* mu;         // [n_steps, P, H, N]
+    union {                   // (one slot, as MvArgs')
+        const double* mu;     // [n_steps, P, H, N]
+        const float* muf;     // BAND kernels: [n_steps, P, H, N] float32 forecasts, read in place of mu
+    };
     const double* sigma;      // [n_steps, P, N, N]
     const int* valid;         // [n_steps, P]
     const float* realized;    // [n_steps, P, N] log-returns of each step's t + 1
@@ -627,7 +738,7 @@ struct MvBt {
 // non-finite value; the host cannot see the values) gets a NaN parameter, which mv_window answers
 // with KMPC_STATUS_SOLVER_ERROR and the hold fallback at every step; so does a cap that is not
 // finite or not > 0 (CAP kernels).
-template <bool GM, bool BOX, bool CAP, bool SWEEP>
+template <bool GM, bool BOX, bool CAP, bool SWEEP, bool BAND = false>
 __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int q, double* lds, double* red) {
     const int N = a0.N, n = a0.N * a0.H;
     int p = q;
@@ -650,14 +761,15 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
             a.gamma = gj; a.c = cj;
             if constexpr (CAP) a.max_turnover = tj;
             a.return_full = 0;
-            a.mu = r.mu + kp * n;
+            if constexpr (BAND) a.muf = r.muf + kp * n;   // (the forecasts: float32, a0.mu unused)
+            else a.mu = r.mu + kp * n;
             a.sigma = r.sigma + kp * N * N;
             a.wp = a0.wp + (size_t)q * N;
             a.wout = a0.wout + (size_t)q * N;
             a.status = a0.status + q;
             a.obj = a0.obj + q;
             a.iters = nullptr;
-            mv_window<GM, BOX, CAP>(a, 0, lds);
+            mv_window<GM, BOX, CAP, BAND>(a, 0, lds);
         } else {
             for (int i = threadIdx.x; i < N; i += blockDim.x) a0.wout[(size_t)q * N + i] = a0.wp[(size_t)q * N + i];
             if (threadIdx.x == 0) {
@@ -683,6 +795,33 @@ __global__ void __launch_bounds__(MAXT) mv_bt_kernel(MvArgs a0, MvBt r) {
         for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, CAP, SWEEP>(a0, r, q, lds, red);
     } else {
         mv_bt_item<false, BOX, CAP, SWEEP>(a0, r, blockIdx.x, lds, red);
+    }
+}
+
+// The band forms (kmpc_solve_mv_band; kmpc_koopman_mv_run: the run alone, no sweep): the same window
+// body and the same item loop with BAND set, under kernel names of their own so that the dense
+// instantiations above keep their symbols. MAXT: 256 for the LDS variant (n <= 256 there), else 1024.
+template <int MAXT, bool GM, bool BOX, bool CAP>
+__global__ void __launch_bounds__(MAXT) mv_band_ipm_kernel(MvArgs a) {
+    extern __shared__ double lds[];
+    if (GM) {
+        for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+            mv_window<true, BOX, CAP, true>(a, b, lds);
+            __syncthreads();
+        }
+    } else {
+        mv_window<false, BOX, CAP, true>(a, blockIdx.x, lds);
+    }
+}
+
+template <int MAXT, bool GM, bool BOX, bool CAP>
+__global__ void __launch_bounds__(MAXT) mv_band_bt_kernel(MvArgs a0, MvBt r) {
+    extern __shared__ double lds[];
+    __shared__ double red[4];   // the bookkeeping's reduction slots (nbt <= 256: four waves)
+    if (GM) {
+        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, CAP, false, true>(a0, r, q, lds, red);
+    } else {
+        mv_bt_item<false, BOX, CAP, false, true>(a0, r, blockIdx.x, lds, red);
     }
 }
 
@@ -764,6 +903,86 @@ size_t mv_cap_workspace_bytes(const kmpc_mv_desc* d) {
     if (!d || d->B <= 0 || mv_cap_in_lds(d->N, d->H)) return 0;
     const size_t slots = d->B < MV_SLOTS ? d->B : MV_SLOTS;
     return sizeof(double) * mv_cap_slab(d->N, d->H) * slots;
+}
+
+// ... and of the band forms: the small arrays of the dense forms; M in the band layout, n (cs + 1)
+// doubles (cs = N | 1 in LDS, N in the slab: bnd), then Y. LDS variant while a window's LDS stays
+// within KMPC_MV_BAND_LDS_BYTES (64 KiB: two windows per CU; n <= 256 follows, since
+// n (N + 1 + H) >= n (2 sqrt(n) + 1) doubles). Past that the slab, n (N + 1) + SH H n doubles.
+static size_t mv_band_lds_bytes(int N, int H, bool cap) {
+    const size_t n = (size_t)N * H;
+    return (cap ? mv_cap_small_bytes(N, H) : mv_small_bytes(N, H)) +
+           sizeof(double) * (n * ((size_t)(N | 1) + 1) + (cap ? 2 : 1) * H * n);
+}
+static bool mv_band_in_lds(int N, int H, bool cap) {
+    return (size_t)N * H <= 256 && mv_band_lds_bytes(N, H, cap) <= KMPC_MV_BAND_LDS_BYTES;
+}
+static size_t mv_band_slab(int N, int H, bool cap) {
+    const size_t n = (size_t)N * H;
+    return n * ((size_t)N + 1) + (cap ? 2 : 1) * H * n;
+}
+size_t mv_band_workspace_bytes(const kmpc_mv_desc* d, bool cap) {
+    if (!d || d->B <= 0 || d->N < 1 || d->H < 1 || mv_band_in_lds(d->N, d->H, cap)) return 0;
+    const size_t slots = d->B < MV_SLOTS ? d->B : MV_SLOTS;
+    return sizeof(double) * mv_band_slab(d->N, d->H, cap) * slots;
+}
+
+// kmpc_solve_mv_band (max_weight, max_turnover: 0 or the active value) and kmpc_koopman_mv_run (bd set:
+// the batch is its P paths): the arguments are checked by the C ABI; here the storage variant, the
+// workspace and the launch.
+int mv_band_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, double max_turnover,
+                   const float* yhat, const double* sigma, size_t sigma_stride, const double* w_prev,
+                   double* w_out, int* status, double* obj, int* iters, int step0, int n_steps, const int* valid,
+                   const float* realized, int n_real, double* value, double* hist, void* ws, size_t ws_bytes,
+                   hipStream_t stream) {
+    const int items = bd ? bd->P : d->B;
+    kmpc_mv_desc di = *d;
+    di.B = items;
+    const bool box = max_weight > 0.0, cap = max_turnover > 0.0;
+    MvArgs a;
+    a.B = items; a.N = d->N; a.H = d->H;
+    a.gamma = d->gamma; a.c = d->cost_coeff;
+    a.allow_short = d->allow_short;
+    a.max_iter = d->max_iter > 0 ? d->max_iter : 100;
+    a.tol = d->tol > 0.0 ? d->tol : 1e-10;
+    a.return_full = bd ? 0 : d->return_full_W;
+    a.muf = yhat; a.sigma = sigma; a.sigma_stride = sigma_stride; a.wp = w_prev;
+    a.wout = w_out; a.status = status; a.obj = obj; a.iters = iters;
+    a.ws = (double*)ws; a.slab = mv_band_slab(d->N, d->H, cap);
+    a.max_weight = max_weight;
+    a.max_turnover = max_turnover;
+    MvBt r;
+    r.P = items; r.items = items; r.n_steps = n_steps; r.n_real = n_real;
+    r.nbt = d->N >= 256 ? 256 : 64 * ((d->N + 63) / 64);   // (backtest_step_launch's block)
+    r.muf = yhat; r.sigma = sigma; r.valid = valid; r.realized = realized;
+    r.gamma = nullptr; r.mv_cost = nullptr; r.bt_cost = nullptr; r.max_turnover = nullptr;
+    r.st.P = items; r.st.N = d->N; r.st.S = bd ? bd->S : 0; r.st.k = step0; r.st.c = bd ? bd->cost_coeff : 0.0;
+    r.st.target = w_out; r.st.realized = nullptr; r.st.w = const_cast<double*>(w_prev); r.st.value = value; r.st.hist = hist;
+    const int n = d->N * d->H;
+    const int nt = 64 * ((n + 63) / 64);   // >= r.nbt
+    const bool in_lds = mv_band_in_lds(d->N, d->H, cap);
+    const size_t small = cap ? mv_cap_small_bytes(d->N, d->H) : mv_small_bytes(d->N, d->H);
+    if (!in_lds) {
+        if (n > 1024 || small > 160 * 1024) return KMPC_ERR_UNSUPPORTED;
+        if (!ws || ws_bytes < mv_band_workspace_bytes(&di, cap)) return KMPC_ERR_WORKSPACE;
+    }
+    const dim3 grid(in_lds ? items : (items < MV_SLOTS ? items : MV_SLOTS));
+    const size_t lds = in_lds ? mv_band_lds_bytes(d->N, d->H, cap) : small;
+    const auto launch = [&](auto bx, auto cp) {
+        constexpr bool BX = decltype(bx)::value, CP = decltype(cp)::value;
+        if (bd) {
+            if (in_lds) hipLaunchKernelGGL((mv_band_bt_kernel<256, false, BX, CP>), grid, dim3(nt), lds, stream, a, r);
+            else hipLaunchKernelGGL((mv_band_bt_kernel<1024, true, BX, CP>), grid, dim3(nt), lds, stream, a, r);
+        } else {
+            if (in_lds) hipLaunchKernelGGL((mv_band_ipm_kernel<256, false, BX, CP>), grid, dim3(nt), lds, stream, a);
+            else hipLaunchKernelGGL((mv_band_ipm_kernel<1024, true, BX, CP>), grid, dim3(nt), lds, stream, a);
+        }
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    if (box) { if (cap) launch(T{}, T{}); else launch(T{}, F{}); }
+    else     { if (cap) launch(F{}, T{}); else launch(F{}, F{}); }
+    return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
 int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma, size_t sigma_stride,

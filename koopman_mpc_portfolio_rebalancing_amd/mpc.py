@@ -335,3 +335,127 @@ def solve_mpc_mean_variance(
     if st not in ("optimal", "optimal_inaccurate"):
         return np.tile(np.asarray(current_weights, dtype=np.float64), (H, 1)), {"status": st}
     return W[0].cpu().numpy(), {"status": st, "value": float(value.item())}
+
+
+# ---- mean-variance MPC, band form: the multi-period solve for a forecast sequence -------------
+
+def _mv_band_program(config: MPCConfig, N: int, H: int) -> Tuple[float, float]:
+    """(u, tau) of the band solve of `config` for [H, N] windows: the active position limit
+    (_box_limit) and turnover cap (_mv_turnover_cap), 0.0 where there is none. Raises ValueError
+    where no program exists or the kernels have no shape for it — gamma negative or not finite, the
+    _box_limit and _mv_turnover_cap rules, H > KMPC_MV_MAX_H or H * N > KMPC_MV_MAX_HN — so that
+    every caller fails before any device work."""
+    g = float(config.gamma)
+    if not np.isfinite(g) or g < 0.0:
+        raise ValueError(f"gamma must be finite and >= 0 (got {config.gamma})")
+    if int(H) < 1 or int(N) < 1:
+        raise ValueError(f"the window must have H >= 1 periods and N >= 1 assets (got H = {H}, N = {N})")
+    if int(H) > _lib.KMPC_MV_MAX_H or int(H) * int(N) > _lib.KMPC_MV_MAX_HN:
+        raise ValueError(f"mean-variance shape H={H}, N={N} exceeds the kernel limits "
+                         f"(H <= {_lib.KMPC_MV_MAX_H}, H*N <= {_lib.KMPC_MV_MAX_HN})")
+    return _box_limit(config, N), _mv_turnover_cap(config)
+
+
+def solve_mpc_mean_variance_banded_batched(
+    current_weights: torch.Tensor,
+    predicted_log_returns: torch.Tensor,
+    cov_matrix: torch.Tensor,
+    config: MPCConfig,
+    return_full: bool = False,
+    with_iters: bool = False,
+):
+    """Batched multi-period mean-variance solve on the band kernels (kmpc_solve_mv_band): the
+    program of solve_mpc_mean_variance_batched with mu_t = yhat_t, the forecast sequence, and the
+    Newton matrix kept and factored as the band matrix it is (half-bandwidth N).
+
+    Args:
+        current_weights: [B, N] device tensor (float64; other dtypes are converted).
+        predicted_log_returns: [B, H, N] forecasts, read by the kernel as float32 — the rollout's
+            yhat goes in as it is; any other dtype is rounded to float32 first.
+        cov_matrix: [B, N, N] per-window covariance, or one shared [N, N].
+        config: MPCConfig — gamma, cost_coeff, allow_short, max_weight and mv_max_turnover are read
+            (max_turnover is not: it is the log-utility solve's, as everywhere in the mean-variance
+            solve). ValueError before any device work on gamma < 0 or not finite, the max_weight /
+            mv_max_turnover rules, or a shape past H <= 16, H * N <= 1,024.
+        return_full: return W [B, H, N] instead of W[:, 0].
+
+    Returns:
+        (W, status, value[, iters]) as solve_mpc_mean_variance_batched.
+    """
+    y = predicted_log_returns
+    if y.dim() != 3:
+        raise ValueError("predicted_log_returns must be [B, H, N]")
+    B, H, N = (int(v) for v in y.shape)
+    u, tau = _mv_band_program(config, N, H)
+    if tuple(current_weights.shape) != (B, N):
+        raise ValueError(f"current_weights must be [{B}, {N}], got {tuple(current_weights.shape)}")
+    S = torch.as_tensor(cov_matrix)
+    if S.dim() == 2 and tuple(S.shape) == (N, N):
+        per_window = 0
+    elif tuple(S.shape) == (B, N, N):
+        per_window = 1
+    else:
+        raise ValueError(f"cov_matrix must be [{N}, {N}] or [{B}, {N}, {N}], got {tuple(S.shape)}")
+    _lib.require_gpu(y)
+    dev = y.device
+    y = y.to(torch.float32).contiguous()
+    wp = current_weights.to(device=dev, dtype=torch.float64).contiguous()
+    S = S.to(device=dev, dtype=torch.float64).contiguous()
+    W = torch.empty((B, H, N) if return_full else (B, N), dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    value = torch.empty(B, dtype=torch.float64, device=dev)
+    iters = torch.empty(B, dtype=torch.int32, device=dev)
+    d = _mv_desc(B, N, H, config, return_full)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        nws = int(L.kmpc_mv_band_workspace_bytes(ctypes.byref(d), int(bool(tau))))
+        ws = _workspace(dev, nws) if nws else None
+        rc = L.kmpc_solve_mv_band(ctypes.byref(d), y.data_ptr(), S.data_ptr(), per_window, wp.data_ptr(), u, tau,
+                                  W.data_ptr(), status.data_ptr(), value.data_ptr(), iters.data_ptr(),
+                                  ws.data_ptr() if ws is not None else None, nws, _lib.stream_handle(dev))
+    _lib.check(rc)
+    if with_iters:
+        return W, status, value, iters
+    return W, status, value
+
+
+def solve_mpc_mean_variance_banded(
+    current_weights: np.ndarray,
+    predicted_log_returns: np.ndarray,
+    cov_matrix: np.ndarray,
+    config: MPCConfig,
+) -> Tuple[np.ndarray, Dict]:
+    """solve_mpc_mean_variance (same signature and return convention) on the band kernels, for a
+    forecast sequence predicted_log_returns [H, N]: returns (W [H, N] float64, info). The forecasts
+    are read as float32 — a float64 input is rounded to float32 (the rollout's yhat is float32
+    already) — so the optimum is that of solve_mpc_mean_variance on the rounded forecasts. Reads
+    gamma, cost_coeff, allow_short, max_weight and mv_max_turnover of `config`; max_turnover is
+    ignored, as the mean-variance solve ignores it everywhere. The band form pays from H = 2 on
+    (profiles/mv_band.md: 4 to 8 times the dense kernel's rate at H = 5 and 10); at H = 1 it is the
+    slower of the two (2.5 times at N = 100) and solve_mpc_mean_variance is the call to use.
+
+    Batched inputs — current_weights [B, N], predicted_log_returns [B, H, N], cov_matrix [B, N, N]
+    or [N, N], arrays or tensors — go to solve_mpc_mean_variance_banded_batched and return its
+    (W [B, H, N], status, value) device tensors."""
+    y = predicted_log_returns
+    if (torch.is_tensor(y) and y.dim() == 3) or (not torch.is_tensor(y) and np.ndim(y) == 3):
+        if not torch.is_tensor(y):
+            _mv_band_program(config, int(np.shape(y)[2]), int(np.shape(y)[1]))   # (errors first)
+            y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32), device=_default_device())
+        wt = current_weights if torch.is_tensor(current_weights) else torch.as_tensor(np.asarray(current_weights, np.float64))
+        St = cov_matrix if torch.is_tensor(cov_matrix) else torch.as_tensor(np.asarray(cov_matrix, np.float64))
+        return solve_mpc_mean_variance_banded_batched(wt, y, St, config, return_full=True)
+    y = np.asarray(y)
+    if y.ndim != 2:
+        raise ValueError("predicted_log_returns must be [H, N] (or [B, H, N])")
+    H, N = y.shape
+    _mv_band_program(config, N, H)
+    dev = _default_device()
+    yt = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32), device=dev).reshape(1, H, N)
+    wt = torch.as_tensor(np.asarray(current_weights, dtype=np.float64), device=dev).reshape(1, N)
+    S = torch.as_tensor(np.asarray(cov_matrix, dtype=np.float64), device=dev)
+    W, status, value = solve_mpc_mean_variance_banded_batched(wt, yt, S, config, return_full=True)
+    st = _lib.STATUS_NAMES.get(int(status.item()), "solver_error")
+    if st not in ("optimal", "optimal_inaccurate"):
+        return np.tile(np.asarray(current_weights, dtype=np.float64), (H, 1)), {"status": st}
+    return W[0].cpu().numpy(), {"status": st, "value": float(value.item())}
