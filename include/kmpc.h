@@ -634,6 +634,42 @@ int kmpc_koopman_mv_run(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvd
                         double* hist, double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
                         void* stream);
 
+/* A sweep of kmpc_koopman_mv_run over the program's hyper-parameters in ONE launch (added within ABI
+ * 0.7.0): n_cfg configs — a risk aversion gamma[j], the solve's cost_coeff mv_cost[j], the
+ * bookkeeping's cost_coeff bt_cost[j], a position limit max_weight[j] and a turnover cap
+ * max_turnover[j], float64 DEVICE arrays [n_cfg] — over the same bdesc->P paths, one workgroup per work
+ * item (config j, path p) (past the LDS variant at most 512 in flight, the others following in the same
+ * workgroups). Rows are config-major, as kmpc_markowitz_sweep: row j * P + p of weights / target
+ * [n_cfg * P, N], value / status / obj [n_cfg * P] and hist [n_cfg * P, S, 4]. The forecasts, the
+ * covariances, valid and the realized returns depend on the path only and are shared by the configs:
+ * yhat [n_steps, P, H, N] f32, sigma [n_steps, P, N, N], valid [n_steps, P], realized [n_real, P, N].
+ * mvdesc's gamma and cost_coeff and bdesc's cost_coeff are not read.
+ *   max_weight:   NULL: no limit in any config. Otherwise every config runs the limit's kernel form
+ *                 under its own max_weight[j], 1 / N < max_weight[j] < 1; with allow_short
+ *                 KMPC_ERR_UNSUPPORTED.
+ *   max_turnover: NULL: no cap in any config. Otherwise every config runs the cap's kernel form under
+ *                 its own max_turnover[j] > 0.
+ * The host cannot see device values: a config with gamma[j] < 0, mv_cost[j] < 0, a max_weight[j] with
+ * N * max_weight[j] <= 1 or >= 1, a max_turnover[j] not > 0, or any of them not finite, ends every
+ * valid step KMPC_STATUS_SOLVER_ERROR with the hold fallback (target = the current weights, turnover
+ * and cost 0); the other configs are not affected.
+ *   workspace: kmpc_mv_band_workspace_bytes of mvdesc with B = n_cfg * P, with_cap = (max_turnover !=
+ *              NULL).
+ * Return codes, all decided before any launch, in this order: the descriptor rules of
+ * kmpc_koopman_mv_run (KMPC_ERR_INVALID, then KMPC_ERR_UNSUPPORTED past the shape limits); n_cfg < 1
+ * or n_cfg * P past an int KMPC_ERR_INVALID; max_weight non-NULL with allow_short
+ * KMPC_ERR_UNSUPPORTED; P == 0 or n_steps == 0 (the shape probe) KMPC_OK; null arrays (gamma, mv_cost
+ * and bt_cost included) KMPC_ERR_INVALID; KMPC_ERR_WORKSPACE. Chunking through step0 as
+ * kmpc_koopman_mv_run. Config j's rows are bit-identical to kmpc_koopman_mv_run with that config's five
+ * scalars (bt_cost[j] as bdesc->cost_coeff; no limit / no cap where the array is NULL). */
+int kmpc_koopman_mv_sweep(const kmpc_backtest_desc* bdesc, const kmpc_mv_desc* mvdesc, int n_cfg,
+                          const double* gamma, const double* mv_cost, const double* bt_cost,
+                          const double* max_weight   /* [n_cfg] device, or NULL: no limit */,
+                          const double* max_turnover /* [n_cfg] device, or NULL: no cap   */,
+                          int step0, int n_steps, const float* yhat, const double* sigma, const int* valid,
+                          const float* realized, int n_real, double* weights, double* value, double* hist,
+                          double* target, int* status, double* obj, void* workspace, size_t ws_bytes, void* stream);
+
 /* Workspace needed by kmpc_rollout / kmpc_solve / kmpc_window (either desc may be NULL; with both,
    the sum for kmpc_window: rollout scratch + yhat + the solve's). */
 size_t kmpc_workspace_bytes(const kmpc_rollout_desc* rdesc, const kmpc_solve_desc* sdesc);
@@ -665,6 +701,8 @@ const char* kmpc_strerror(int code);
    changed.
    kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run were added within 0.7.0 in
    the same way: three new functions (and the constant KMPC_MV_BAND_LDS_BYTES), no struct, enum or
+   existing function changed.
+   kmpc_koopman_mv_sweep was added within 0.7.0 in the same way: one new function, no struct, enum or
    existing function changed. */
 const char* kmpc_version(void);
 

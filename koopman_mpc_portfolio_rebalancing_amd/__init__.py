@@ -12,7 +12,8 @@ from .koopman import DeviceKoopman, KoopmanModelSpec, standardize_panel  # noqa:
 from .backtest import (BacktestConfig, BuyAndHoldStrategy, KoopmanMPCStrategy, Strategy,  # noqa: F401
                        calculate_metrics, run_backtest, run_backtest_lockstep, run_backtest_sweep,
                        sweep_backtest)
-from .baselines import (KoopmanMVStrategy, run_koopman_mv_lockstep, run_markowitz_lockstep,  # noqa: F401
-                        run_markowitz_sweep, sweep_backtest_markowitz)
+from .baselines import (KoopmanMVStrategy, run_koopman_mv_lockstep, run_koopman_mv_sweep,  # noqa: F401
+                        run_markowitz_lockstep, run_markowitz_sweep, sweep_backtest_koopman_mv,
+                        sweep_backtest_markowitz)
 
 __version__ = "0.7.0"

@@ -45,7 +45,7 @@ PACK_MIN_B = 512     # KMPC_PACK_MIN_B: AUTO packs N <= 32 windows 2-4 per wave 
 # and kmpc_solve_mv_box, then kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep,
 # then kmpc_backtest_run_box and kmpc_backtest_sweep_box, then kmpc_solve_box_workspace_bytes and kmpc_solve_box_ws,
 # then kmpc_mv_cap_workspace_bytes, kmpc_solve_mv_cap, kmpc_markowitz_run_cap and kmpc_markowitz_sweep_cap,
-# then kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run
+# then kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run, then kmpc_koopman_mv_sweep
 # were added within 0.7.0 (new functions only: nothing a 0.7.0 caller uses changed); a 0.7.0 library
 # built before them lacks the symbols, which load() reports
 ABI_VERSION = "0.7.0"
@@ -131,6 +131,8 @@ def _signatures() -> dict:
         "kmpc_solve_mv_band": (ci, [md, vp, vp, ci, vp, cd, cd, vp, vp, vp, vp, vp, sz, vp]),
         "kmpc_koopman_mv_run": (ci, [bd, md, cd, cd, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, sz,
                                      vp]),
+        "kmpc_koopman_mv_sweep": (ci, [bd, md, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
+                                       vp, vp, sz, vp]),
     }
 
 

@@ -20,6 +20,7 @@ moments (``run_markowitz_sweep`` / ``sweep_backtest_markowitz``: kmpc_markowitz_
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Any, Dict, Optional, Sequence
 
 import numpy as np
@@ -28,7 +29,7 @@ import torch
 
 from . import _lib
 from .backtest import (METRIC_NAMES, PREROLL_CHUNK, BacktestConfig, KoopmanMPCStrategy, Strategy, _cache_hit,
-                       _cache_key, _env_stats, _prepare_paths, run_backtest)
+                       _cache_key, _env_stats, _prepare_paths, _sweep_fields, run_backtest)
 from .koopman import KoopmanModelSpec
 from .mpc import (MPCConfig, _box_limit, _mv_band_program, _mv_desc, _mv_turnover_cap, _workspace,
                   solve_mpc_mean_variance_banded_batched, solve_mpc_mean_variance_batched)
@@ -608,6 +609,185 @@ def run_koopman_mv_lockstep(strategy: "KoopmanMVStrategy", obs, realized, config
     return _markowitz_out(hist, w, metrics, S, (P,))
 
 
+# ---- the sweep of the mean-variance Koopman-MPC backtest -----------------------------------------
+
+_MV_SWEEP_FREE = ("gamma", "cost_coeff", "mv_max_turnover", "max_weight")   # the kernel's per-config parameters
+
+
+def _mv_sweep_configs(mpc_configs, N: int) -> tuple:
+    """The configs of a mean-variance sweep and their programs [(u, tau)] (_mv_band_program, for N
+    assets): the configs may differ in gamma, cost_coeff, mv_max_turnover and max_weight only, and each
+    must be a program of the band solve with cost_coeff >= 0. Raises ValueError, no device work."""
+    cfgs = list(mpc_configs)
+    if not cfgs:
+        raise ValueError("mpc_configs is empty")
+    f0 = _sweep_fields(cfgs[0], _MV_SWEEP_FREE)
+    for j, c in enumerate(cfgs):
+        fj = _sweep_fields(c, _MV_SWEEP_FREE)
+        if fj != f0:
+            diff = sorted(k for k in set(f0) | set(fj) if f0.get(k) != fj.get(k))
+            raise ValueError(f"mpc_configs[{j}] differs from mpc_configs[0] in {diff}: a sweep varies "
+                             "gamma, cost_coeff, mv_max_turnover and max_weight only")
+    H = int(cfgs[0].horizon)
+    programs = []
+    for j, c in enumerate(cfgs):
+        try:
+            programs.append(_mv_band_program(c, N, H))
+            cc = float(c.cost_coeff)
+            if not np.isfinite(cc) or cc < 0.0:
+                raise ValueError(f"cost_coeff must be finite and >= 0 (got {c.cost_coeff})")
+        except ValueError as e:
+            raise ValueError(f"mpc_configs[{j}]: {e}") from None
+    return cfgs, programs
+
+
+def _mv_sweep_groups(programs: Sequence[tuple]) -> list:
+    """The launches of a mean-variance sweep: the limit and the cap are compile-time forms of the kernel,
+    so the configs go in up to four groups by (has an active limit, has a cap) of their programs
+    [(u, tau)] (u = 0: none — _box_limit gives 0 for an inactive max_weight >= 1). Returns
+    [(has_limit, has_cap, [config indices, increasing])] for the non-empty groups, every config in one."""
+    groups = {}
+    for j, (u, tau) in enumerate(programs):
+        groups.setdefault((bool(u), bool(tau)), []).append(j)
+    return [(box, cap, groups[(box, cap)]) for box in (False, True) for cap in (False, True) if (box, cap) in groups]
+
+
+def _mv_sweep_scatter(parts: Sequence[torch.Tensor], groups: list, C: int) -> torch.Tensor:
+    """The groups' rows [C_g, ...] back in the configs' order: [C, ...]."""
+    full = parts[0].new_empty((C,) + tuple(parts[0].shape[1:]))
+    for part, (_, _, idx) in zip(parts, groups):
+        full[torch.as_tensor(idx, device=part.device)] = part
+    return full
+
+
+def run_koopman_mv_sweep(strategy: "KoopmanMVStrategy", obs, realized, config: BacktestConfig, mean, std,
+                         mpc_configs: Sequence[MPCConfig], bt_cost_coeffs: Optional[Sequence[float]] = None,
+                         lookback_window: int = 60, n_rows: Optional[int] = None) -> Dict[str, Any]:
+    """A hyper-parameter sweep of run_koopman_mv_lockstep: C configs (MPCConfig.gamma, cost_coeff,
+    mv_max_turnover and max_weight; BacktestConfig.cost_coeff) over the same P paths, every step of
+    every (config, path) in kmpc_koopman_mv_sweep launches, one workgroup each — an efficient frontier
+    (a gamma grid) at P = 1 fills C compute units where C lock-step runs keep one busy, one after the
+    other. The forecasts and the rolling covariances depend on the path only: per chunk of steps they are
+    rolled out and computed once for the P paths (chunked as run_koopman_mv_lockstep, within
+    MARKOWITZ_SIGMA_BYTES and PREROLL_CHUNK) and shared by the configs.
+
+    Args:
+        strategy: its model is used; the solve's program comes from mpc_configs.
+        obs, realized, config, mean, std, lookback_window, n_rows: as run_koopman_mv_lockstep
+            (config.cost_coeff is the default of bt_cost_coeffs).
+        mpc_configs: C MPCConfigs that differ in gamma, cost_coeff, mv_max_turnover and max_weight only;
+            each a program of the band solve (_mv_band_program) with cost_coeff >= 0. ValueError
+            otherwise, before any device work.
+        bt_cost_coeffs: the bookkeeping's cost_coeff per config (default config.cost_coeff for all).
+    The position limit and the turnover cap are compile-time forms of the kernel: the configs run in up
+    to four launches per chunk, grouped by (has an active limit, has a cap) (_mv_sweep_groups), each over
+    the same forecasts and covariances, with the limit and the cap per config inside a group. Config j's
+    rows equal run_koopman_mv_lockstep with that config (and its bt_cost_coeff) bit for bit.
+    Returns: the run_koopman_mv_lockstep dict with a leading config axis — portfolio_value / return /
+        turnover / cost [C, P, S], weights [C, P, N], metrics {name: [C, P]} — and "status" [C, P]
+        int32, the last step's solve status of each work item (0 after a held step).
+    """
+    x, r = torch.as_tensor(obs), torch.as_tensor(realized)
+    if x.dim() != 3 or r.dim() != 3 or x.shape[:2] != r.shape[:2] or x.shape[2] < r.shape[2]:
+        raise ValueError("obs must be [P, T, >= N] and realized [P, T, N]")
+    P, T, N = (int(v) for v in r.shape)
+    cfgs, programs = _mv_sweep_configs(mpc_configs, N)
+    C, H = len(cfgs), int(cfgs[0].horizon)
+    btc = [float(config.cost_coeff)] * C if bt_cost_coeffs is None else [float(v) for v in bt_cost_coeffs]
+    if len(btc) != C:
+        raise ValueError(f"bt_cost_coeffs has {len(btc)} entries for {C} configs")
+    if len(np.atleast_1d(np.asarray(mean))) < N or len(np.atleast_1d(np.asarray(std))) < N:
+        raise ValueError(f"mean and std must have {N} entries")
+    groups = _mv_sweep_groups(programs)
+    km = strategy.device_model()
+    pp = _prepare_paths(km, x, r, config, mean, std, n_rows)
+    S, dev = pp.S, km.device
+    z = pp.x.contiguous()
+    ts32 = pp.steps_t.to(torch.int32)
+    f64 = dict(dtype=torch.float64, device=dev)
+    L = _lib.load()
+    bd = _lib.BacktestDesc(P, N, max(S, 1), 0.0)
+    state = []   # per group: the descriptor, the configs' device arrays and the work items' rows
+    with torch.cuda.device(dev):
+        sh = _lib.stream_handle(dev)
+        for box, cap, idx in groups:
+            Cg = len(idx)
+            g = SimpleNamespace(md=_mv_desc(Cg * P, N, H, cfgs[0], False), C=Cg)
+            g.par = [torch.tensor([float(getattr(cfgs[j], name)) for j in idx], **f64) for name in ("gamma", "cost_coeff")]
+            g.par.append(torch.tensor([btc[j] for j in idx], **f64))
+            g.par.append(torch.tensor([programs[j][0] for j in idx], **f64) if box else None)
+            g.par.append(torch.tensor([programs[j][1] for j in idx], **f64) if cap else None)
+            g.head = (ctypes.byref(bd), ctypes.byref(g.md), Cg) + tuple(t.data_ptr() if t is not None else None for t in g.par)
+            _lib.check(L.kmpc_koopman_mv_sweep(*g.head, 0, 0, None, None, None, None, 0, None, None, None, None, None,
+                                               None, None, 0, sh))   # (shape check only)
+            g.w = torch.full((Cg, P, N), 1.0 / N, **f64)       # backtest.py:161
+            g.value = torch.full((Cg, P), float(config.initial_capital), **f64)
+            g.hist = torch.empty((Cg, P, max(S, 1), 4), **f64)
+            g.target = torch.empty((Cg * P, N), **f64)
+            g.status = torch.zeros((Cg, P), dtype=torch.int32, device=dev)
+            g.obj = torch.empty((Cg * P,), **f64)
+            g.nws = int(L.kmpc_mv_band_workspace_bytes(ctypes.byref(g.md), int(cap)))
+            state.append(g)
+        metrics = torch.empty((C * P, 5), **f64)
+        if P and S:
+            nws = max(g.nws for g in state)
+            ws = _workspace(dev, nws) if nws else None   # (one buffer: the groups' launches follow each other on the stream)
+            sc = max(1, min(_markowitz_chunk(P, N), PREROLL_CHUNK // P))
+            for k0 in range(0, S, sc):
+                n = min(sc, S - k0)
+                y = km.rollout(pp.xt[pp.steps_t[k0:k0 + n]].reshape(n * P, -1), pp.m, pp.sd, H, N).contiguous()
+                mu = torch.empty((n, P, N), **f64)   # (the rolling mean: not read, mu is the forecast)
+                sigma = torch.empty((n, P, N, N), **f64)
+                valid = torch.empty((n, P), dtype=torch.int32, device=dev)
+                _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback_window), z.data_ptr(), int(z.shape[2]),
+                                                        pp.m.data_ptr(), pp.sd.data_ptr(), ts32[k0:k0 + n].data_ptr(),
+                                                        mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), sh))
+                tn = pp.steps_t[k0:k0 + n] + 1
+                n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
+                rr = pp.rt[tn[:n_real]].contiguous() if n_real else None
+                for g in state:
+                    _lib.check(L.kmpc_koopman_mv_sweep(
+                        *g.head, k0, n, y.data_ptr(), sigma.data_ptr(), valid.data_ptr(),
+                        rr.data_ptr() if rr is not None else None, n_real, g.w.data_ptr(), g.value.data_ptr(),
+                        g.hist.data_ptr(), g.target.data_ptr(), g.status.data_ptr(), g.obj.data_ptr(),
+                        ws.data_ptr() if ws is not None and g.nws else None, g.nws, sh))
+        hist = _mv_sweep_scatter([g.hist for g in state], groups, C)
+        w = _mv_sweep_scatter([g.w for g in state], groups, C)
+        status = _mv_sweep_scatter([g.status for g in state], groups, C)
+        if P and S:
+            dm = _lib.BacktestDesc(C * P, N, max(S, 1), 0.0)
+            _lib.check(L.kmpc_backtest_metrics(ctypes.byref(dm), hist.data_ptr(), metrics.data_ptr(), sh))
+    out = _markowitz_out(hist, w, metrics, S, (C, P))
+    out["status"] = status
+    return out
+
+
+def sweep_backtest_koopman_mv(strategy: "KoopmanMVStrategy", env: Any, config: BacktestConfig,
+                              mpc_configs: Sequence[MPCConfig], lookback_window: int = 60) -> list:
+    """run_backtest(KoopmanMVStrategy(model, mpc_configs[j]), env, config) for C configs on one
+    environment in one sweep (run_koopman_mv_sweep with P = 1): the env-level counterpart of
+    sweep_backtest_markowitz for the risk-aware row — a gamma grid gives the efficient frontier. The
+    configs may differ in gamma, cost_coeff, mv_max_turnover and max_weight only (ValueError otherwise,
+    and on a config that is no program of the band solve, before any device work). Returns C DataFrames
+    with the reference's columns (date, portfolio_value, return, turnover, cost), the rebalance_freq
+    quirk kept. An env without stats (custom de-standardisation) runs run_backtest per config."""
+    cfgs, _ = _mv_sweep_configs(mpc_configs, int(env.n_assets))
+    st = _env_stats(env)
+    if st is None:
+        km = strategy.device_model()
+        return [run_backtest(KoopmanMVStrategy(km, c), env, config, verbose=False) for c in cfgs]
+    data = env.test_dataset.data
+    rets = env.destandardize_returns(env.extract_current_returns(data))
+    n_rows = len(env.test_dataset)
+    out = run_koopman_mv_sweep(strategy, torch.as_tensor(data)[None], torch.as_tensor(rets)[None], config, st[0], st[1],
+                               cfgs, lookback_window=lookback_window, n_rows=n_rows)
+    steps = range(0, n_rows - config.horizon, config.rebalance_freq)
+    dates = [env.test_dataset.dates[t] for t in steps]
+    cols = {k: out[k][:, 0].cpu().numpy() for k in ("portfolio_value", "return", "turnover", "cost")}
+    return [pd.DataFrame({"date": dates, **{k: v[j] for k, v in cols.items()}}) for j in range(len(cfgs))]
+
+
 __all__: Sequence[str] = ("DMDStrategy", "MarkowitzStrategy", "fit_dmd", "dmd_model_spec",
                           "rolling_moments", "Strategy", "run_markowitz_lockstep", "run_markowitz_sweep",
-                          "sweep_backtest_markowitz", "KoopmanMVStrategy", "run_koopman_mv_lockstep")
+                          "sweep_backtest_markowitz", "KoopmanMVStrategy", "run_koopman_mv_lockstep",
+                          "run_koopman_mv_sweep", "sweep_backtest_koopman_mv")

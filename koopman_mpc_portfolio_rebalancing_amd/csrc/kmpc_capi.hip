@@ -411,6 +411,30 @@ int kmpc_koopman_mv_run(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, dou
                                 ws_bytes, (hipStream_t)stream);
 }
 
+int kmpc_koopman_mv_sweep(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, int n_cfg, const double* gamma,
+                          const double* mv_cost, const double* bt_cost, const double* max_weight,
+                          const double* max_turnover, int step0, int n_steps, const float* yhat, const double* sigma,
+                          const int* valid, const float* realized, int n_real, double* weights, double* value,
+                          double* hist, double* target, int* status, double* obj, void* workspace, size_t ws_bytes,
+                          void* stream) {
+    // kmpc_koopman_mv_run's rules in its order, all before any launch; the limits and the caps are device
+    // values (checked per config in the kernel), so of their rules only allow_short is decided here
+    if (!bd || !d || bd->P < 0 || bd->N < 1 || bd->S < 1 || step0 < 0 || n_steps < 0 ||
+        step0 + n_steps > bd->S || n_real < 0 || n_real > n_steps || d->N != bd->N || d->H < 1 ||
+        d->return_full_W)
+        return KMPC_ERR_INVALID;
+    if (d->H > KMPC_MV_MAX_H || (long long)d->N * d->H > KMPC_MV_MAX_HN) return KMPC_ERR_UNSUPPORTED;
+    if (n_cfg < 1 || (long long)n_cfg * bd->P > 0x7fffffffLL) return KMPC_ERR_INVALID;
+    if (max_weight && d->allow_short) return KMPC_ERR_UNSUPPORTED;
+    if (bd->P == 0 || n_steps == 0) return KMPC_OK;
+    if (!gamma || !mv_cost || !bt_cost || !yhat || !sigma || !valid || !weights || !value || !hist || !target ||
+        !status || !obj || (n_real > 0 && !realized))
+        return KMPC_ERR_INVALID;
+    return kmpc::mv_band_launch(bd, d, 0.0, 0.0, yhat, sigma, (size_t)d->N * d->N, weights, target, status, obj,
+                                nullptr, step0, n_steps, valid, realized, n_real, value, hist, workspace, ws_bytes,
+                                (hipStream_t)stream, n_cfg, gamma, mv_cost, bt_cost, max_weight, max_turnover);
+}
+
 int kmpc_rolling_moments(int B, int T, int N, int lookback, const float* z, int ldz,
                          const float* mean, const float* std, const int* ts,
                          double* mu, double* sigma, int* valid, void* stream) {

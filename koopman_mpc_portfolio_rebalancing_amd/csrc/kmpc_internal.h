@@ -47,13 +47,17 @@ int mv_solve_launch(const kmpc_mv_desc* d, const double* mu, const double* sigma
                     void* ws, size_t ws_bytes, hipStream_t stream, double max_weight = 0.0,   // > 0: the BOX kernels
                     double max_turnover = 0.0);   // > 0: the CAP kernels (workspace: mv_cap_workspace_bytes)
 // the band forms (BAND kernels): the workspace (0 in the LDS case) and the launch of kmpc_solve_mv_band
-// (bd null) or of kmpc_koopman_mv_run (bd set: w_prev = the weights, w_out = the target rows)
+// (bd null) or of kmpc_koopman_mv_run (bd set: w_prev = the weights, w_out = the target rows) or of
+// kmpc_koopman_mv_sweep (bd set, n_cfg > 0: n_cfg x P rows; the configs' device arrays [n_cfg], the last
+// two null or set for the whole launch: the BOX / CAP form; max_weight and max_turnover are not read)
 size_t mv_band_workspace_bytes(const kmpc_mv_desc* d, bool cap);
 int mv_band_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, double max_turnover,
                    const float* yhat, const double* sigma, size_t sigma_stride, const double* w_prev,
                    double* w_out, int* status, double* obj, int* iters, int step0, int n_steps, const int* valid,
                    const float* realized, int n_real, double* value, double* hist, void* ws, size_t ws_bytes,
-                   hipStream_t stream);
+                   hipStream_t stream, int n_cfg = 0, const double* cfg_gamma = nullptr,
+                   const double* cfg_mv_cost = nullptr, const double* cfg_bt_cost = nullptr,
+                   const double* cfg_max_weight = nullptr, const double* cfg_max_turnover = nullptr);
 int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, int ldz, const float* mean,
                            const float* stdv, const int* ts, double* mu, double* sigma, int* valid,
                            hipStream_t stream);

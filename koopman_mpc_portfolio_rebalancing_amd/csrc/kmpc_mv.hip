@@ -729,6 +729,8 @@ struct MvBt {
     const double* bt_cost;    // SWEEP: [C] device, the bookkeeping's cost_coeff
     const double* max_turnover;   // SWEEP of the CAP kernels: [C] device, the solve's turnover cap
     bt::StepArgs st;          // st.k = the first step's history row; st.target = the W0 rows [items, N]
+    const double* max_weight; // SWEEP of the BAND BOX kernels: [C] device, the solve's position limit (null: a0's).
+                              // After st: every field above keeps its offset
 };
 
 // a0: the solve's program; a0.wp = the weights [items, N] (each step's w_prev: the item's current,
@@ -737,7 +739,7 @@ struct MvBt {
 // optimal and obj NaN. SWEEP: a config outside the program (gamma < 0, cost_coeff < 0 or a
 // non-finite value; the host cannot see the values) gets a NaN parameter, which mv_window answers
 // with KMPC_STATUS_SOLVER_ERROR and the hold fallback at every step; so does a cap that is not
-// finite or not > 0 (CAP kernels).
+// finite or not > 0 (CAP kernels), and a per-config limit outside 1 / N < u < 1 (band BOX sweep).
 template <bool GM, bool BOX, bool CAP, bool SWEEP, bool BAND = false>
 __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int q, double* lds, double* red) {
     const int N = a0.N, n = a0.N * a0.H;
@@ -753,6 +755,17 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
     }
     double tj = a0.max_turnover;
     if constexpr (SWEEP && CAP) tj = r.max_turnover[q / r.P];
+    // The config's own position limit (the band sweep alone: the dense sweeps have one limit per launch
+    // and keep their instruction streams). mv_window's start assumes 1 / N < u < 1: a limit outside
+    // that, or a non-finite one, never reaches it: the config's gamma becomes NaN, as a bad gamma[j].
+    double uj = a0.max_weight;
+    if constexpr (SWEEP && BOX && BAND) {
+        if (r.max_weight) {
+            const double v = r.max_weight[q / r.P];
+            if (isfinite(v) && v < 1.0 && N * v > 1.0) uj = v;
+            else gj = __builtin_nan("");
+        }
+    }
     const size_t PN = (size_t)r.P * N;
     for (int k = 0; k < r.n_steps; ++k) {
         const size_t kp = (size_t)k * r.P + p;
@@ -760,6 +773,7 @@ __device__ __forceinline__ void mv_bt_item(const MvArgs& a0, const MvBt& r, int 
             MvArgs a = a0;
             a.gamma = gj; a.c = cj;
             if constexpr (CAP) a.max_turnover = tj;
+            if constexpr (SWEEP && BOX && BAND) a.max_weight = uj;
             a.return_full = 0;
             if constexpr (BAND) a.muf = r.muf + kp * n;   // (the forecasts: float32, a0.mu unused)
             else a.mu = r.mu + kp * n;
@@ -798,8 +812,8 @@ __global__ void __launch_bounds__(MAXT) mv_bt_kernel(MvArgs a0, MvBt r) {
     }
 }
 
-// The band forms (kmpc_solve_mv_band; kmpc_koopman_mv_run: the run alone, no sweep): the same window
-// body and the same item loop with BAND set, under kernel names of their own so that the dense
+// The band forms (kmpc_solve_mv_band; kmpc_koopman_mv_run and, with SWEEP, kmpc_koopman_mv_sweep): the
+// same window body and the same item loop with BAND set, under kernel names of their own so that the dense
 // instantiations above keep their symbols. MAXT: 256 for the LDS variant (n <= 256 there), else 1024.
 template <int MAXT, bool GM, bool BOX, bool CAP>
 __global__ void __launch_bounds__(MAXT) mv_band_ipm_kernel(MvArgs a) {
@@ -814,14 +828,14 @@ __global__ void __launch_bounds__(MAXT) mv_band_ipm_kernel(MvArgs a) {
     }
 }
 
-template <int MAXT, bool GM, bool BOX, bool CAP>
+template <int MAXT, bool GM, bool BOX, bool CAP, bool SWEEP>
 __global__ void __launch_bounds__(MAXT) mv_band_bt_kernel(MvArgs a0, MvBt r) {
     extern __shared__ double lds[];
     __shared__ double red[4];   // the bookkeeping's reduction slots (nbt <= 256: four waves)
     if (GM) {
-        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, CAP, false, true>(a0, r, q, lds, red);
+        for (int q = blockIdx.x; q < r.items; q += gridDim.x) mv_bt_item<true, BOX, CAP, SWEEP, true>(a0, r, q, lds, red);
     } else {
-        mv_bt_item<false, BOX, CAP, false, true>(a0, r, blockIdx.x, lds, red);
+        mv_bt_item<false, BOX, CAP, SWEEP, true>(a0, r, blockIdx.x, lds, red);
     }
 }
 
@@ -927,18 +941,27 @@ size_t mv_band_workspace_bytes(const kmpc_mv_desc* d, bool cap) {
     return sizeof(double) * mv_band_slab(d->N, d->H, cap) * slots;
 }
 
-// kmpc_solve_mv_band (max_weight, max_turnover: 0 or the active value) and kmpc_koopman_mv_run (bd set:
-// the batch is its P paths): the arguments are checked by the C ABI; here the storage variant, the
-// workspace and the launch.
+// kmpc_solve_mv_band (max_weight, max_turnover: 0 or the active value), kmpc_koopman_mv_run (bd set:
+// the batch is its P paths) and kmpc_koopman_mv_sweep (bd set and n_cfg > 0: the batch is n_cfg x P work
+// items, config-major; the five cfg_ arrays [n_cfg] are device memory, cfg_max_weight / cfg_max_turnover
+// non-null pick the BOX / CAP form and the two scalars are not read): the arguments are checked by the
+// C ABI; here the storage variant, the workspace and the launch.
 int mv_band_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, double max_turnover,
                    const float* yhat, const double* sigma, size_t sigma_stride, const double* w_prev,
                    double* w_out, int* status, double* obj, int* iters, int step0, int n_steps, const int* valid,
                    const float* realized, int n_real, double* value, double* hist, void* ws, size_t ws_bytes,
-                   hipStream_t stream) {
-    const int items = bd ? bd->P : d->B;
+                   hipStream_t stream, int n_cfg, const double* cfg_gamma, const double* cfg_mv_cost,
+                   const double* cfg_bt_cost, const double* cfg_max_weight, const double* cfg_max_turnover) {
+    const bool sweep = bd && n_cfg > 0;
+    const int items = sweep ? n_cfg * bd->P : bd ? bd->P : d->B;
     kmpc_mv_desc di = *d;
     di.B = items;
-    const bool box = max_weight > 0.0, cap = max_turnover > 0.0;
+    const bool box = sweep ? cfg_max_weight != nullptr : max_weight > 0.0;
+    const bool cap = sweep ? cfg_max_turnover != nullptr : max_turnover > 0.0;
+    if (sweep) {   // (the configs' own: a0's limit is what a config with a bad limit is handed, inside 1 / N < u < 1)
+        max_weight = box ? 0.5 * (1.0 + 1.0 / d->N) : 0.0;
+        max_turnover = 0.0;
+    }
     MvArgs a;
     a.B = items; a.N = d->N; a.H = d->H;
     a.gamma = d->gamma; a.c = d->cost_coeff;
@@ -952,11 +975,13 @@ int mv_band_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double m
     a.max_weight = max_weight;
     a.max_turnover = max_turnover;
     MvBt r;
-    r.P = items; r.items = items; r.n_steps = n_steps; r.n_real = n_real;
+    r.P = sweep ? bd->P : items; r.items = items; r.n_steps = n_steps; r.n_real = n_real;
     r.nbt = d->N >= 256 ? 256 : 64 * ((d->N + 63) / 64);   // (backtest_step_launch's block)
     r.muf = yhat; r.sigma = sigma; r.valid = valid; r.realized = realized;
-    r.gamma = nullptr; r.mv_cost = nullptr; r.bt_cost = nullptr; r.max_turnover = nullptr;
-    r.st.P = items; r.st.N = d->N; r.st.S = bd ? bd->S : 0; r.st.k = step0; r.st.c = bd ? bd->cost_coeff : 0.0;
+    r.gamma = cfg_gamma; r.mv_cost = cfg_mv_cost; r.bt_cost = cfg_bt_cost; r.max_turnover = cfg_max_turnover;
+    r.max_weight = cfg_max_weight;
+    r.st.P = items; r.st.N = d->N; r.st.S = bd ? bd->S : 0; r.st.k = step0;
+    r.st.c = bd && !sweep ? bd->cost_coeff : 0.0;   // (sweep: the config's bt_cost)
     r.st.target = w_out; r.st.realized = nullptr; r.st.w = const_cast<double*>(w_prev); r.st.value = value; r.st.hist = hist;
     const int n = d->N * d->H;
     const int nt = 64 * ((n + 63) / 64);   // >= r.nbt
@@ -970,9 +995,12 @@ int mv_band_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double m
     const size_t lds = in_lds ? mv_band_lds_bytes(d->N, d->H, cap) : small;
     const auto launch = [&](auto bx, auto cp) {
         constexpr bool BX = decltype(bx)::value, CP = decltype(cp)::value;
-        if (bd) {
-            if (in_lds) hipLaunchKernelGGL((mv_band_bt_kernel<256, false, BX, CP>), grid, dim3(nt), lds, stream, a, r);
-            else hipLaunchKernelGGL((mv_band_bt_kernel<1024, true, BX, CP>), grid, dim3(nt), lds, stream, a, r);
+        if (sweep) {
+            if (in_lds) hipLaunchKernelGGL((mv_band_bt_kernel<256, false, BX, CP, true>), grid, dim3(nt), lds, stream, a, r);
+            else hipLaunchKernelGGL((mv_band_bt_kernel<1024, true, BX, CP, true>), grid, dim3(nt), lds, stream, a, r);
+        } else if (bd) {
+            if (in_lds) hipLaunchKernelGGL((mv_band_bt_kernel<256, false, BX, CP, false>), grid, dim3(nt), lds, stream, a, r);
+            else hipLaunchKernelGGL((mv_band_bt_kernel<1024, true, BX, CP, false>), grid, dim3(nt), lds, stream, a, r);
         } else {
             if (in_lds) hipLaunchKernelGGL((mv_band_ipm_kernel<256, false, BX, CP>), grid, dim3(nt), lds, stream, a);
             else hipLaunchKernelGGL((mv_band_ipm_kernel<1024, true, BX, CP>), grid, dim3(nt), lds, stream, a);
@@ -1068,6 +1096,7 @@ int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max
     r.nbt = d->N >= 256 ? 256 : 64 * ((d->N + 63) / 64);   // (backtest_step_launch's block)
     r.mu = mu; r.sigma = sigma; r.valid = valid; r.realized = realized;
     r.gamma = gamma; r.mv_cost = mv_cost; r.bt_cost = bt_cost; r.max_turnover = cfg_turnover;
+    r.max_weight = nullptr;   // (the dense sweeps: one limit per launch, a.max_weight)
     r.st.P = items; r.st.N = d->N; r.st.S = bd->S; r.st.k = step0; r.st.c = sweep ? 0.0 : bd->cost_coeff;
     r.st.target = target; r.st.realized = nullptr; r.st.w = weights; r.st.value = value; r.st.hist = hist;
     const bool box = max_weight > 0.0;
