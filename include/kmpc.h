@@ -509,6 +509,48 @@ int kmpc_rolling_moments_paths(int P, int n_ts, int T, int N, int lookback, cons
                                const float* mean, const float* std, const int* ts,
                                double* mu, double* sigma, int* valid, void* stream);
 
+/* ---- Rolling covariance with a choice of estimator (added within ABI 0.7.0) ------------------- */
+/* kmpc_rolling_moments / _paths with the covariance estimator chosen by the caller: the same windows
+ * (rows lo .. hi - 1 of panel p for test row ts[s], n = hi - lo rows, p = N assets), the same float32
+ * returns r_s = z_s * std + mean widened to float64, the same mu (the float32-rounded plain mean, for
+ * every estimator) and the same valid; a window with valid = 0 is still filled from the rows it has.
+ * Every estimator returns its Sigma + 1e-6 I, exactly symmetric (sigma == sigma^T bit for bit).
+ *   KMPC_COV_SAMPLE       np.cov (ddof 1): the call IS kmpc_rolling_moments / _paths, bit for bit.
+ *   KMPC_COV_LEDOIT_WOLF  x_s = r_s - mean(r) (float64), G = X'X, S = G / n, m = tr(S) / p,
+ *                         beta_ = sum_s (||x_s||^2)^2, delta_ = ||G||_F^2 / n^2,
+ *                         beta = (beta_ / n - delta_) / (p n), delta = (delta_ - 2 m tr(S) + p m^2) / p,
+ *                         beta <- min(beta, delta), rho = 0 if beta == 0 (or delta == 0) else beta / delta,
+ *                         Sigma = (1 - rho) S + rho m I      (sklearn.covariance.ledoit_wolf).
+ *   KMPC_COV_OAS          the same S and m; alpha = ||S||_F^2 / p^2, num = alpha + m^2,
+ *                         den = (n + 1) (alpha - m^2 / p), rho = 1 if den == 0 else min(num / den, 1),
+ *                         Sigma = (1 - rho) S + rho m I      (sklearn.covariance.oas).
+ *   KMPC_COV_EWMA         omega_s = lambda^(hi-1-s) / sum_k lambda^k, m_w = sum_s omega_s r_s,
+ *                         Sigma = sum_s omega_s (r_s - m_w)(r_s - m_w)'
+ *                         (np.cov(aweights = omega, ddof = 0); lambda = 1: the 1/n sample covariance).
+ * A window of n <= 1 rows or of constant rows gives Sigma = 1e-6 I (rho = 0 for Ledoit-Wolf, 1 for OAS),
+ * never a NaN. The Gram matrix runs on the float64 matrix cores from the float32 panel, so any lookback
+ * runs; every sum has a fixed order: a window's bits do not depend on the batch around it.
+ *   estimator:   KMPC_COV_*; another value is KMPC_ERR_INVALID.
+ *   ewma_lambda: read by KMPC_COV_EWMA alone: outside (0, 1] or NaN is KMPC_ERR_INVALID.
+ *   shrinkage:   [B] (or [n_ts, P]) float64, rho per window (0 for SAMPLE and EWMA); may be NULL.
+ * Rules, each decided before any launch: the shape rules of kmpc_rolling_moments / _paths
+ * (KMPC_ERR_INVALID), then the estimator, then lambda, then N > KMPC_MAX_N with an estimator other than
+ * SAMPLE (KMPC_ERR_UNSUPPORTED), then an empty batch (KMPC_OK), then null arrays (KMPC_ERR_INVALID). */
+enum kmpc_cov_estimator {
+    KMPC_COV_SAMPLE = 0,
+    KMPC_COV_LEDOIT_WOLF = 1,
+    KMPC_COV_OAS = 2,
+    KMPC_COV_EWMA = 3
+};
+int kmpc_rolling_cov(int B, int T, int N, int lookback, const float* z, int ldz,
+                     const float* mean, const float* std, const int* ts,
+                     double* mu, double* sigma, int* valid,
+                     int estimator, double ewma_lambda, double* shrinkage, void* stream);
+int kmpc_rolling_cov_paths(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                           const float* mean, const float* std, const int* ts,
+                           double* mu, double* sigma, int* valid,
+                           int estimator, double ewma_lambda, double* shrinkage, void* stream);
+
 /* ---- Markowitz backtest: run_backtest(MarkowitzStrategy(...)) for P paths in ONE launch -------- */
 /* (added within ABI 0.7.0) Steps step0 .. step0 + n_steps - 1 of every path, each the strategy's
  * window — kmpc_solve_mv_ws (kmpc_solve_mv_box under a limit) of that step's moments from the path's
@@ -703,7 +745,9 @@ const char* kmpc_strerror(int code);
    the same way: three new functions (and the constant KMPC_MV_BAND_LDS_BYTES), no struct, enum or
    existing function changed.
    kmpc_koopman_mv_sweep was added within 0.7.0 in the same way: one new function, no struct, enum or
-   existing function changed. */
+   existing function changed.
+   kmpc_rolling_cov and kmpc_rolling_cov_paths were added within 0.7.0 in the same way: two new
+   functions and the new enum kmpc_cov_estimator, no struct, existing enum or existing function changed. */
 const char* kmpc_version(void);
 
 #ifdef __cplusplus

@@ -32,6 +32,8 @@ STATUS_NAMES = {0: "optimal", 1: "optimal_inaccurate", 2: "infeasible", 3: "unbo
 KMPC_MV_MAX_HN = 1024    # mean-variance solve: H * N per workgroup (> 128: workspace-resident matrix)
 KMPC_MV_MAX_H = 16
 
+COV_ESTIMATOR = {"sample": 0, "ledoit_wolf": 1, "oas": 2, "ewma": 3}   # enum kmpc_cov_estimator (KMPC_COV_*)
+
 PATH_AUTO, PATH_REGISTER, PATH_LARGE, PATH_REGISTER_UNPACKED = 0, 1, 2, 3   # kmpc_solve_desc.path
 PRECISION_AUTO, PRECISION_F64, PRECISION_MIXED = 0, 1, 2   # kmpc_solve_desc.precision
 MIXED_MIN_B = 2048   # KMPC_MIXED_MIN_B: AUTO runs the mixed pair from this many windows per call
@@ -45,7 +47,8 @@ PACK_MIN_B = 512     # KMPC_PACK_MIN_B: AUTO packs N <= 32 windows 2-4 per wave 
 # and kmpc_solve_mv_box, then kmpc_rolling_moments_paths, kmpc_markowitz_run and kmpc_markowitz_sweep,
 # then kmpc_backtest_run_box and kmpc_backtest_sweep_box, then kmpc_solve_box_workspace_bytes and kmpc_solve_box_ws,
 # then kmpc_mv_cap_workspace_bytes, kmpc_solve_mv_cap, kmpc_markowitz_run_cap and kmpc_markowitz_sweep_cap,
-# then kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run, then kmpc_koopman_mv_sweep
+# then kmpc_mv_band_workspace_bytes, kmpc_solve_mv_band and kmpc_koopman_mv_run, then kmpc_koopman_mv_sweep,
+# then kmpc_rolling_cov and kmpc_rolling_cov_paths (with the enum kmpc_cov_estimator)
 # were added within 0.7.0 (new functions only: nothing a 0.7.0 caller uses changed); a 0.7.0 library
 # built before them lacks the symbols, which load() reports
 ABI_VERSION = "0.7.0"
@@ -133,6 +136,8 @@ def _signatures() -> dict:
                                      vp]),
         "kmpc_koopman_mv_sweep": (ci, [bd, md, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
                                        vp, vp, sz, vp]),
+        "kmpc_rolling_cov": (ci, [ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, cd, vp, vp]),
+        "kmpc_rolling_cov_paths": (ci, [ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, cd, vp, vp]),
     }
 
 

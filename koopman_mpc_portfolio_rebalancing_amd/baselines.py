@@ -15,7 +15,9 @@ kmpc_solve_mv_cap under an L1 turnover cap) run on the
 device, for one window (``rebalance``) or many (``rebalance_batch``). A whole Markowitz backtest of P
 paths runs on the device too (``run_markowitz_lockstep``: every step of a path in one
 kmpc_markowitz_run launch), as does a sweep of the baseline's two hyper-parameters over shared
-moments (``run_markowitz_sweep`` / ``sweep_backtest_markowitz``: kmpc_markowitz_sweep).
+moments (``run_markowitz_sweep`` / ``sweep_backtest_markowitz``: kmpc_markowitz_sweep). The rolling
+covariance the mean-variance strategies read has a choice of estimator (``cov_estimator``: the
+reference's sample covariance, Ledoit-Wolf, OAS or EWMA; kmpc_rolling_cov), routed in one place.
 """
 from __future__ import annotations
 
@@ -68,7 +70,41 @@ class DMDStrategy(KoopmanMPCStrategy):
         super().__init__(dmd_model_spec(self.K), mpc_config, device)
 
 
-def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None, std=None):
+COV_ESTIMATORS = tuple(_lib.COV_ESTIMATOR)   # "sample", "ledoit_wolf", "oas", "ewma"
+
+
+def _cov_estimator(estimator: str = "sample", ewma_lambda: float = 0.94) -> tuple:
+    """(KMPC_COV_* code, lambda) of a covariance estimator's name; ValueError on an unknown name or,
+    for "ewma", a lambda outside (0, 1] (the rules of kmpc_rolling_cov, before any device work)."""
+    if estimator not in _lib.COV_ESTIMATOR:
+        raise ValueError(f"unknown covariance estimator {estimator!r}: one of {', '.join(COV_ESTIMATORS)}")
+    lam = float(ewma_lambda)
+    if estimator == "ewma" and not (0.0 < lam <= 1.0):
+        raise ValueError(f"ewma_lambda must lie in (0, 1] (got {ewma_lambda})")
+    return _lib.COV_ESTIMATOR[estimator], lam
+
+
+def _strategy_cov(strategy) -> tuple:
+    """The (code, lambda) of a strategy's cov_estimator / cov_ewma_lambda ("sample" where it has none)."""
+    return _cov_estimator(getattr(strategy, "cov_estimator", "sample"), getattr(strategy, "cov_ewma_lambda", 0.94))
+
+
+def _rolling_cov_paths(cov: tuple, P: int, n: int, T: int, N: int, lookback: int, z, m, sd, ts, mu, sigma, valid,
+                       sh) -> None:
+    """The covariances of n test rows ts of the P panels z [P, T, ld] under the estimator cov
+    (_cov_estimator) into mu [n, P, N], sigma [n, P, N, N], valid [n, P]: the one place the backtests
+    route the estimator. "sample" is kmpc_rolling_moments_paths, the others kmpc_rolling_cov_paths."""
+    L = _lib.load()
+    head = (P, n, T, N, int(lookback), z.data_ptr(), int(z.shape[2]), m.data_ptr(), sd.data_ptr(), ts.data_ptr(),
+            mu.data_ptr(), sigma.data_ptr(), valid.data_ptr())
+    if cov[0] == _lib.COV_ESTIMATOR["sample"]:
+        _lib.check(L.kmpc_rolling_moments_paths(*head, sh))
+    else:
+        _lib.check(L.kmpc_rolling_cov_paths(*head, cov[0], cov[1], None, sh))
+
+
+def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None, std=None,
+                    estimator: str = "sample", ewma_lambda: float = 0.94, return_shrinkage: bool = False):
     """Markowitz moments on the device (baselines.py:70-88) for the windows t in ``ts``.
 
     Args:
@@ -76,11 +112,17 @@ def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None
             current returns, data_finance.py:717-729).
         ts: test indices; window t uses rows max(0, t + 1 - lookback) .. t.
         mean, std: [N] de-standardization (data_finance.py:740-742); None -> identity.
+        estimator: the covariance's estimator — "sample" (np.cov, the reference's), "ledoit_wolf",
+            "oas" (shrinkage towards tr(S) / N I, as sklearn.covariance) or "ewma" (exponentially
+            weighted with decay ``ewma_lambda`` in (0, 1]); kmpc_rolling_cov. mu does not depend on it.
+            ValueError on an unknown name or a bad lambda, before any device work.
+        return_shrinkage: also return the shrinkage rho [B] float64 (0 for "sample" and "ewma").
 
     Returns:
-        mu [B, N] float64 (float32-rounded mean), sigma [B, N, N] float64 (np.cov + 1e-6 I),
+        mu [B, N] float64 (float32-rounded mean), sigma [B, N, N] float64 (the estimate + 1e-6 I),
         valid [B] int32 (t + 1 >= 5).
     """
+    cov = _cov_estimator(estimator, ewma_lambda)
     _lib.require_gpu(z)
     dev = z.device
     N = int(n_assets)
@@ -98,12 +140,17 @@ def rolling_moments(z: torch.Tensor, ts, lookback: int, n_assets: int, mean=None
     sigma = torch.empty((B, N, N), dtype=torch.float64, device=dev)
     valid = torch.empty(B, dtype=torch.int32, device=dev)
     L = _lib.load()
+    head = (B, T, N, int(lookback), z.data_ptr(), int(z.stride(0)), m.data_ptr(), sd.data_ptr(), tt.data_ptr(),
+            mu.data_ptr(), sigma.data_ptr(), valid.data_ptr())
+    rho = torch.empty(B, dtype=torch.float64, device=dev) if return_shrinkage else None
     with torch.cuda.device(dev):
-        rc = L.kmpc_rolling_moments(B, T, N, int(lookback), z.data_ptr(), int(z.stride(0)), m.data_ptr(),
-                                    sd.data_ptr(), tt.data_ptr(), mu.data_ptr(), sigma.data_ptr(),
-                                    valid.data_ptr(), _lib.stream_handle(dev))
+        if estimator == "sample" and rho is None:
+            rc = L.kmpc_rolling_moments(*head, _lib.stream_handle(dev))
+        else:
+            rc = L.kmpc_rolling_cov(*head, cov[0], cov[1], rho.data_ptr() if rho is not None else None,
+                                    _lib.stream_handle(dev))
     _lib.check(rc)
-    return mu, sigma, valid
+    return (mu, sigma, valid, rho) if return_shrinkage else (mu, sigma, valid)
 
 
 class _LimitKeyword(type(Strategy)):
@@ -111,10 +158,13 @@ class _LimitKeyword(type(Strategy)):
     class call and applied with ``set_max_weight`` / ``set_max_turnover`` — ``__init__`` keeps the
     reference's three arguments exactly (baselines.py:33-37), as the drop-in surface promises."""
 
-    def __call__(cls, *args, max_weight: float = 0.0, max_turnover: float = 0.0, **kwargs):
+    def __call__(cls, *args, max_weight: float = 0.0, max_turnover: float = 0.0, cov_estimator: str = "sample",
+                 cov_ewma_lambda: float = 0.94, **kwargs):
+        _cov_estimator(cov_estimator, cov_ewma_lambda)   # (ValueError before the strategy exists)
         obj = super().__call__(*args, **kwargs)
         obj.set_max_weight(max_weight)
         obj.set_max_turnover(max_turnover)
+        obj.set_cov_estimator(cov_estimator, cov_ewma_lambda)
         return obj
 
 
@@ -130,7 +180,10 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
     the L1 turnover cap of ``MPCConfig.mv_max_turnover``: every target keeps
     ||w - current_weights||_1 <= max_turnover (0: none, the reference's program), the cap the MPC
     strategies trade under (MPCConfig.max_turnover). A step whose current weights lie further than
-    the cap from the feasible set (under a position limit only) holds them.
+    the cap from the feasible set (under a position limit only) holds them. ``cov_estimator`` and
+    ``cov_ewma_lambda`` (keywords, not in the reference; ``set_cov_estimator``) choose the estimator of
+    the rolling covariance: "sample" (the reference's np.cov, the default), "ledoit_wolf", "oas" or
+    "ewma" (rolling_moments); the rolling mean does not depend on it.
     """
 
     def __init__(self, risk_aversion: float = 1.0, cost_coeff: float = 0.001, allow_short: bool = False):
@@ -139,6 +192,8 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         self.allow_short = allow_short
         self.max_weight = 0.0
         self.max_turnover = 0.0
+        self.cov_estimator = "sample"
+        self.cov_ewma_lambda = 0.94
         self.mpc_config = MPCConfig(horizon=1, gamma=risk_aversion, cost_coeff=cost_coeff,
                                     allow_short=allow_short, solver="ECOS")
         self._dev = None
@@ -153,6 +208,13 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         """Set the L1 turnover cap on the strategy and in its ``mpc_config`` (mv_max_turnover)."""
         self.max_turnover = max_turnover
         self.mpc_config.mv_max_turnover = max_turnover
+
+    def set_cov_estimator(self, cov_estimator: str = "sample", cov_ewma_lambda: float = 0.94) -> None:
+        """Set the covariance estimator of the rolling moments ("sample", "ledoit_wolf", "oas" or
+        "ewma" with its decay); ValueError on an unknown name or a lambda outside (0, 1]."""
+        _cov_estimator(cov_estimator, cov_ewma_lambda)
+        self.cov_estimator = cov_estimator
+        self.cov_ewma_lambda = float(cov_ewma_lambda)
 
     def _device(self) -> torch.device:
         if self._dev is None:
@@ -186,7 +248,8 @@ class MarkowitzStrategy(Strategy, metaclass=_LimitKeyword):
         z, mean, std, N = self._returns(env)
         dev = z.device
         wp = torch.as_tensor(np.asarray(current_weights, np.float64), device=dev).reshape(len(ts), N)
-        mu, sigma, valid = rolling_moments(z, ts, lookback_window, N, mean, std)
+        mu, sigma, valid = rolling_moments(z, ts, lookback_window, N, mean, std, estimator=self.cov_estimator,
+                                           ewma_lambda=self.cov_ewma_lambda)
         W0, status, value = solve_mpc_mean_variance_batched(wp, mu.unsqueeze(1), sigma, self.mpc_config)
         hold = valid == 0   # fewer than 5 past rows: keep the current weights (baselines.py:76-78)
         W0 = torch.where(hold.unsqueeze(1), wp, W0)
@@ -227,6 +290,7 @@ def _markowitz_paths(strategy, obs, realized, config: BacktestConfig, mean, std,
     H = int(strategy.mpc_config.horizon)
     u = _box_limit(strategy.mpc_config, N)
     tau = _mv_turnover_cap(strategy.mpc_config)
+    cov = _strategy_cov(strategy)
     n_rows = T if n_rows is None else int(n_rows)
     steps = list(range(0, n_rows - config.horizon, config.rebalance_freq))
     dev = strategy._device()
@@ -237,14 +301,14 @@ def _markowitz_paths(strategy, obs, realized, config: BacktestConfig, mean, std,
     if m.numel() != N or sd.numel() != N:
         raise ValueError(f"mean and std must have {N} entries")
     return SimpleNamespace(z=z, rt=rt, P=P, T=T, N=N, H=H, u=u, tau=tau, steps=steps, S=len(steps), dev=dev, m=m, sd=sd,
-                           ts=torch.as_tensor(steps, dtype=torch.int32, device=dev))
+                           cov=cov, ts=torch.as_tensor(steps, dtype=torch.int32, device=dev))
 
 
 def _markowitz_chunks(pp, lookback: int):
     """Per chunk of steps: (k0, n, mu [n, P, H, N], sigma [n, P, N, N], valid [n, P], the realized rows
-    [n_real, P, N] of the steps' t + 1 or None, n_real). One kmpc_rolling_moments_paths per chunk; a
+    [n_real, P, N] of the steps' t + 1 or None, n_real). One kmpc_rolling_moments_paths per chunk
+    (kmpc_rolling_cov_paths under the strategy's estimator: _rolling_cov_paths); a
     horizon above 1 repeats the rolling mean in every period (the reference's strategy has H = 1)."""
-    L = _lib.load()
     P, T, N, H, dev = pp.P, pp.T, pp.N, pp.H, pp.dev
     sc = _markowitz_chunk(P, N)
     for k0 in range(0, pp.S, sc):
@@ -253,9 +317,7 @@ def _markowitz_chunks(pp, lookback: int):
         sigma = torch.empty((n, P, N, N), dtype=torch.float64, device=dev)
         valid = torch.empty((n, P), dtype=torch.int32, device=dev)
         ts = pp.ts[k0:k0 + n]
-        _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback), pp.z.data_ptr(), int(pp.z.shape[2]),
-                                                pp.m.data_ptr(), pp.sd.data_ptr(), ts.data_ptr(), mu.data_ptr(),
-                                                sigma.data_ptr(), valid.data_ptr(), _lib.stream_handle(dev)))
+        _rolling_cov_paths(pp.cov, P, n, T, N, lookback, pp.z, pp.m, pp.sd, ts, mu, sigma, valid, _lib.stream_handle(dev))
         mu = mu[:, :, None, :].expand(n, P, H, N).contiguous()
         tn = [t + 1 for t in pp.steps[k0:k0 + n] if t + 1 < T]   # (steps increase: a prefix has a t + 1)
         rr = pp.rt[torch.as_tensor(tn, dtype=torch.long, device=dev)].contiguous() if tn else None
@@ -428,8 +490,8 @@ def run_markowitz_sweep(strategy: "MarkowitzStrategy", obs, realized, config: Ba
 def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Sequence["MarkowitzStrategy"]) -> list:
     """run_backtest(strategies[j], env, config) for C Markowitz strategies on one environment in one
     sweep (run_markowitz_sweep with P = 1): the env-level counterpart of sweep_backtest. The
-    strategies may differ in risk_aversion, cost_coeff and max_turnover only, and must be all capped
-    or all uncapped (ValueError otherwise, before any device work). Returns C DataFrames with the reference's columns (date, portfolio_value, return,
+    strategies may differ in risk_aversion, cost_coeff and max_turnover only, must be all capped
+    or all uncapped and must share their covariance estimator (ValueError otherwise, before any device work). Returns C DataFrames with the reference's columns (date, portfolio_value, return,
     turnover, cost), the rebalance_freq quirk kept. An env without stats (custom de-standardisation)
     runs run_backtest per strategy."""
     strats = list(strategies)
@@ -447,6 +509,10 @@ def sweep_backtest_markowitz(env: Any, config: BacktestConfig, strategies: Seque
         if int(s.mpc_config.horizon) != int(s0.mpc_config.horizon):
             raise ValueError(f"strategies[{j}] differs from strategies[0] in horizon: a sweep varies "
                              "risk_aversion, cost_coeff and max_turnover only")
+        cj, c0 = _strategy_cov(s), _strategy_cov(s0)
+        if cj[0] != c0[0] or (s0.cov_estimator == "ewma" and cj[1] != c0[1]):
+            raise ValueError(f"strategies[{j}] differs from strategies[0] in cov_estimator: the covariances are "
+                             "computed once and shared; a sweep varies risk_aversion, cost_coeff and max_turnover only")
     st = _env_stats(env)
     n = getattr(env, "n_assets", None)
     if st is None or n is None:
@@ -478,12 +544,19 @@ class KoopmanMVStrategy(KoopmanMPCStrategy):
         mpc_config: MPCConfig — horizon, gamma, cost_coeff, allow_short, max_weight and
             mv_max_turnover are read (max_turnover is the log-utility solve's and is not).
         device: as KoopmanMPCStrategy.
+        cov_estimator, cov_ewma_lambda: the estimator of the rolling covariance, as MarkowitzStrategy's
+            ("sample", "ledoit_wolf", "oas", "ewma"; ValueError on an unknown name or a lambda outside
+            (0, 1]). The lock-step run and the sweep read it from the strategy: one estimator for all configs.
     A run_backtest(strategy, env, config) drives it as any Strategy; run_koopman_mv_lockstep runs P
     such backtests on the device.
     """
 
-    def __init__(self, model: Any, mpc_config: MPCConfig, device: str = "cpu"):
+    def __init__(self, model: Any, mpc_config: MPCConfig, device: str = "cpu", cov_estimator: str = "sample",
+                 cov_ewma_lambda: float = 0.94):
+        _cov_estimator(cov_estimator, cov_ewma_lambda)
         super().__init__(model, mpc_config, device)
+        self.cov_estimator = cov_estimator
+        self.cov_ewma_lambda = float(cov_ewma_lambda)
         self._ret_cache = (None, None)
 
     def _returns(self, env):
@@ -516,7 +589,8 @@ class KoopmanMVStrategy(KoopmanMPCStrategy):
             y_std = km.rollout(obs, np.zeros(N), np.ones(N), H, N)
             yhat = torch.as_tensor(env.destandardize_returns(y_std), device=km.device, dtype=torch.float32)
         z, mean, std = self._returns(env)
-        _, sigma, valid = rolling_moments(z, ts, lookback_window, N, mean, std)
+        _, sigma, valid = rolling_moments(z, ts, lookback_window, N, mean, std, estimator=self.cov_estimator,
+                                          ewma_lambda=self.cov_ewma_lambda)
         W0, status, value = solve_mpc_mean_variance_banded_batched(wp, yhat, sigma, self.mpc_config)
         W0 = torch.where((valid == 0).unsqueeze(1), wp, W0)   # fewer than 5 past rows: hold
         W0 = W0.cpu().numpy()
@@ -551,6 +625,7 @@ def run_koopman_mv_lockstep(strategy: "KoopmanMVStrategy", obs, realized, config
     cfg = strategy.mpc_config
     H = int(cfg.horizon)
     u, tau = _mv_band_program(cfg, N, H)
+    cov = _strategy_cov(strategy)
     if len(np.atleast_1d(np.asarray(mean))) < N or len(np.atleast_1d(np.asarray(std))) < N:
         raise ValueError(f"mean and std must have {N} entries")
     km = strategy.device_model()
@@ -585,9 +660,7 @@ def run_koopman_mv_lockstep(strategy: "KoopmanMVStrategy", obs, realized, config
                 mu = torch.empty((n, P, N), **f64)   # (the rolling mean: not read, mu is the forecast)
                 sigma = torch.empty((n, P, N, N), **f64)
                 valid = torch.empty((n, P), dtype=torch.int32, device=dev)
-                _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback_window), z.data_ptr(), int(z.shape[2]),
-                                                        pp.m.data_ptr(), pp.sd.data_ptr(), ts32[k0:k0 + n].data_ptr(),
-                                                        mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), sh))
+                _rolling_cov_paths(cov, P, n, T, N, lookback_window, z, pp.m, pp.sd, ts32[k0:k0 + n], mu, sigma, valid, sh)
                 tn = pp.steps_t[k0:k0 + n] + 1
                 n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
                 rr = pp.rt[tn[:n_real]].contiguous() if n_real else None
@@ -692,6 +765,7 @@ def run_koopman_mv_sweep(strategy: "KoopmanMVStrategy", obs, realized, config: B
         raise ValueError("obs must be [P, T, >= N] and realized [P, T, N]")
     P, T, N = (int(v) for v in r.shape)
     cfgs, programs = _mv_sweep_configs(mpc_configs, N)
+    cov = _strategy_cov(strategy)   # (the strategy's estimator, shared by the configs)
     C, H = len(cfgs), int(cfgs[0].horizon)
     btc = [float(config.cost_coeff)] * C if bt_cost_coeffs is None else [float(v) for v in bt_cost_coeffs]
     if len(btc) != C:
@@ -739,9 +813,7 @@ def run_koopman_mv_sweep(strategy: "KoopmanMVStrategy", obs, realized, config: B
                 mu = torch.empty((n, P, N), **f64)   # (the rolling mean: not read, mu is the forecast)
                 sigma = torch.empty((n, P, N, N), **f64)
                 valid = torch.empty((n, P), dtype=torch.int32, device=dev)
-                _lib.check(L.kmpc_rolling_moments_paths(P, n, T, N, int(lookback_window), z.data_ptr(), int(z.shape[2]),
-                                                        pp.m.data_ptr(), pp.sd.data_ptr(), ts32[k0:k0 + n].data_ptr(),
-                                                        mu.data_ptr(), sigma.data_ptr(), valid.data_ptr(), sh))
+                _rolling_cov_paths(cov, P, n, T, N, lookback_window, z, pp.m, pp.sd, ts32[k0:k0 + n], mu, sigma, valid, sh)
                 tn = pp.steps_t[k0:k0 + n] + 1
                 n_real = int((tn < T).sum().item())   # (steps increase: the rows with a t + 1 are a prefix)
                 rr = pp.rt[tn[:n_real]].contiguous() if n_real else None
@@ -775,7 +847,9 @@ def sweep_backtest_koopman_mv(strategy: "KoopmanMVStrategy", env: Any, config: B
     st = _env_stats(env)
     if st is None:
         km = strategy.device_model()
-        return [run_backtest(KoopmanMVStrategy(km, c), env, config, verbose=False) for c in cfgs]
+        cov = dict(cov_estimator=getattr(strategy, "cov_estimator", "sample"),
+                   cov_ewma_lambda=getattr(strategy, "cov_ewma_lambda", 0.94))
+        return [run_backtest(KoopmanMVStrategy(km, c, **cov), env, config, verbose=False) for c in cfgs]
     data = env.test_dataset.data
     rets = env.destandardize_returns(env.extract_current_returns(data))
     n_rows = len(env.test_dataset)

@@ -456,6 +456,37 @@ int kmpc_rolling_moments_paths(int P, int n_ts, int T, int N, int lookback, cons
                                               (hipStream_t)stream);
 }
 
+// kmpc_rolling_cov / _paths: the estimator's rules after the shape rules, all before any launch
+static int rolling_cov_rules(int N, int estimator, double ewma_lambda) {
+    if (estimator < KMPC_COV_SAMPLE || estimator > KMPC_COV_EWMA) return KMPC_ERR_INVALID;
+    if (estimator == KMPC_COV_EWMA && !(ewma_lambda > 0.0 && ewma_lambda <= 1.0)) return KMPC_ERR_INVALID;   // (NaN too)
+    if (estimator != KMPC_COV_SAMPLE && N > KMPC_MAX_N) return KMPC_ERR_UNSUPPORTED;
+    return KMPC_OK;
+}
+
+int kmpc_rolling_cov(int B, int T, int N, int lookback, const float* z, int ldz, const float* mean,
+                     const float* std, const int* ts, double* mu, double* sigma, int* valid, int estimator,
+                     double ewma_lambda, double* shrinkage, void* stream) {
+    if (B < 0 || T < 0 || N < 1 || lookback < 1 || ldz < N) return KMPC_ERR_INVALID;
+    if (const int rc = rolling_cov_rules(N, estimator, ewma_lambda)) return rc;
+    if (B == 0) return KMPC_OK;
+    if (!z || !mean || !std || !ts || !mu || !sigma || !valid) return KMPC_ERR_INVALID;
+    return kmpc::rolling_cov_paths_launch(1, B, T, N, lookback, z, ldz, mean, std, ts, mu, sigma, valid, estimator,
+                                          ewma_lambda, shrinkage, (hipStream_t)stream);
+}
+
+int kmpc_rolling_cov_paths(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz, const float* mean,
+                           const float* std, const int* ts, double* mu, double* sigma, int* valid, int estimator,
+                           double ewma_lambda, double* shrinkage, void* stream) {
+    if (P < 0 || n_ts < 0 || T < 0 || N < 1 || lookback < 1 || ldz < N) return KMPC_ERR_INVALID;
+    if ((long long)P * n_ts > 0x7fffffffLL) return KMPC_ERR_INVALID;
+    if (const int rc = rolling_cov_rules(N, estimator, ewma_lambda)) return rc;
+    if (P == 0 || n_ts == 0) return KMPC_OK;
+    if (!z || !mean || !std || !ts || !mu || !sigma || !valid) return KMPC_ERR_INVALID;
+    return kmpc::rolling_cov_paths_launch(P, n_ts, T, N, lookback, z, ldz, mean, std, ts, mu, sigma, valid, estimator,
+                                          ewma_lambda, shrinkage, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 namespace {

@@ -64,6 +64,11 @@ int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, in
 int rolling_moments_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
                                  const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
                                  int* valid, hipStream_t stream);
+// kmpc_rolling_cov (P = 1) / kmpc_rolling_cov_paths: KMPC_COV_SAMPLE is rolling_moments_paths_launch,
+// the others rolling_cov_kernel; shrinkage [n_ts, P] may be null
+int rolling_cov_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                             const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
+                             int* valid, int estimator, double lambda, double* shrinkage, hipStream_t stream);
 // the Markowitz backtest: the run (n_cfg = 0) or the sweep of n_cfg configs; cap: the CAP kernels with
 // the run's max_turnover or the sweep's per-config caps cfg_turnover [n_cfg] (device)
 int mv_bt_launch(const kmpc_backtest_desc* bd, const kmpc_mv_desc* d, double max_weight, bool cap,

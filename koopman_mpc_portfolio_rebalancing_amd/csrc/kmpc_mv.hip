@@ -1,5 +1,6 @@
 // kmpc_mv.hip — batched mean-variance MPC solve (replaces solve_mpc_mean_variance, mpc.py:119-184),
-// the Markowitz rolling moments (MarkowitzStrategy.rebalance, baselines.py:70-88) and the Markowitz
+// the Markowitz rolling moments (MarkowitzStrategy.rebalance, baselines.py:70-88), their covariance
+// under a shrinkage or an exponentially weighted estimator (rolling_cov_kernel) and the Markowitz
 // backtest of P paths, every step of a path in one workgroup (mv_bt_kernel, further down).
 //
 // Program per window (mpc.py:128, 145-172):
@@ -878,6 +879,222 @@ __global__ void rolling_moments_kernel(int P, int T, int N, int lookback, const 
     }
 }
 
+// The covariance estimators of kmpc_rolling_cov (Ledoit-Wolf, OAS, EWMA) for the windows of
+// rolling_moments_kernel — same grid (window b = s P + p), same rows lo .. hi - 1, same valid, same
+// float32 returns r = z * std + mean and the same mu (the float32-rounded plain mean) — with the Gram
+// matrix on v_mfma_f64_16x16x4_f64. With x_s = r_s - mean (float64; EWMA: the omega-weighted mean):
+//   Ledoit-Wolf / OAS:  G = X'X, S = G / n, m = tr(S) / p, Sigma = (1 - rho) S + (rho m + 1e-6) I with
+//                       rho from tr(S), ||G||_F^2 and sum_s ||x_s||^4 (include/kmpc.h has the formulas);
+//   EWMA:               Sigma = sum_s omega_s x_s x_s' + 1e-6 I, omega_s = lambda^(hi-1-s) / sum_k lambda^k.
+// Passes, all over the float32 panel (nothing of the window is staged, so any lookback runs):
+//   1. the means, one column per thread, into LDS;
+//   2. (shrinkage only) sum_s ||x_s||^2 and sum_s ||x_s||^4, one row per wave at a time;
+//   3. (shrinkage only) the Gram tiles once for ||G||_F^2 alone — rho scales every entry, and the tiles of
+//      N = 1024 do not fit the registers, so they are formed again in pass 4 rather than stored raw, read
+//      back and stored again (the same instructions on the same operands: the same bits as the norm saw);
+//   4. the Gram tiles again, scaled and stored.
+// A wave takes the 16 x 16 tiles (I <= J) of the upper block triangle round-robin and walks the window
+// from its last row back in k-steps of 4 (lane l: column l & 15 of the tile, row l >> 4 of the step), so
+// the EWMA weight is a running product that may underflow to 0 only where the weight is 0; each return
+// is formed once per element per tile pass. Operands are 0 past the window and past column N. The A
+// operand carries omega for EWMA, so (i, j) and (j, i) would round differently: only i <= j is taken from
+// the accumulators and the mirror is that same value — off-diagonal tiles through a per-wave LDS
+// transpose (both stores run along a row of Sigma), diagonal tiles entry by entry. Every sum has a fixed
+// order (sequential, butterfly, then the waves' slots in order): the same window gives the same bits in
+// any batch.
+typedef double cov_d4 __attribute__((ext_vector_type(4)));
+constexpr int COV_THREADS = 256, COV_WAVES = COV_THREADS / 64, COV_TLD = 17;   // (tile rows padded: 17 doubles)
+constexpr int COV_KU = 4;   // k-steps (of 4 rows) per trip of the Gram loop
+
+__host__ __device__ inline size_t cov_lds_doubles(int N) {
+    return (size_t)N + (size_t)COV_WAVES * 16 * COV_TLD + 3 * COV_WAVES;
+}
+
+__global__ void __launch_bounds__(COV_THREADS)
+rolling_cov_kernel(int P, int T, int N, int lookback, const float* zp, int ldz, const float* mean,
+                   const float* stdv, const int* ts, double* mu, double* sigma, int* valid, int estimator,
+                   double lambda, double* shrinkage) {
+    extern __shared__ double cl[];
+    double* ml = cl;                                  // [N] the centring means
+    double* tbuf = cl + N;                            // [COV_WAVES][16][COV_TLD] the waves' transpose tiles
+    double* red = tbuf + COV_WAVES * 16 * COV_TLD;    // [3][COV_WAVES] reduction slots
+    const int b = blockIdx.x;
+    const int sb = b / P;
+    const float* z = zp + (size_t)(b - sb * P) * T * ldz;
+    const int t = ts[sb];
+    const int hi = min(t + 1, T), lo = max(0, hi - lookback), rows = max(hi - lo, 0);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool ew = estimator == KMPC_COV_EWMA;
+    if (threadIdx.x == 0) valid[b] = (t + 1 >= 5 && t < T) ? 1 : 0;
+    auto ret = [&](int s, int j) -> float {
+#pragma clang fp contract(off)
+        const float p = z[(size_t)s * ldz + j] * stdv[j];
+        return p + mean[j];
+    };
+    // sum_k lambda^k over the window's rows (every thread: the same sequence, the same bits)
+    double wsum = 0.0;
+    if (ew) {
+        double pw = 1.0;
+        for (int k = 0; k < rows; ++k) { wsum += pw; pw *= lambda; }
+    }
+    const double winv = (ew && rows > 0) ? 1.0 / wsum : 0.0;
+    for (int j = threadIdx.x; j < N; j += blockDim.x) {
+        double acc = 0.0;
+        for (int s = lo; s < hi; ++s) acc += (double)ret(s, j);
+        const double m = rows > 0 ? acc / rows : 0.0;
+        mu[(size_t)b * N + j] = (double)(float)m;
+        if (ew) {
+            double wa = 0.0, pw = 1.0;
+            for (int s = hi - 1; s >= lo; --s) { wa += pw * (double)ret(s, j); pw *= lambda; }
+            ml[j] = wa * winv;
+        } else {
+            ml[j] = m;
+        }
+    }
+    __syncthreads();
+
+    const int NB = (N + 15) / 16, ntile = NB * (NB + 1) / 2;
+    const int cl16 = lane & 15, kk = lane >> 4;
+    const double l4 = (lambda * lambda) * (lambda * lambda);
+    const double w0 = (kk == 0 ? 1.0 : kk == 1 ? lambda : kk == 2 ? lambda * lambda : lambda * lambda * lambda) * winv;
+    auto tile_of = [&](int q, int& I, int& J) {
+        int rem = q;
+        I = 0;
+        while (rem >= NB - I) { rem -= NB - I; ++I; }
+        J = I + rem;
+    };
+    // tile (I, J) of sum_s [omega_s] x_s x_s': rows (lane >> 4) + 4 r, column lane & 15 in acc[r]
+    auto gram_tile = [&](int I, int J) -> cov_d4 {
+        const int ca = 16 * I + cl16, cb = 16 * J + cl16;
+        const bool ina = ca < N, inb = cb < N;
+        const float sa = ina ? stdv[ca] : 0.f, ma = ina ? mean[ca] : 0.f;
+        const float sb_ = inb ? stdv[cb] : 0.f, mb = inb ? mean[cb] : 0.f;
+        const double ca_m = ina ? ml[ca] : 0.0, cb_m = inb ? ml[cb] : 0.0;
+        const float* za = z + (ina ? ca : 0);
+        const float* zb = z + (inb ? cb : 0);
+        cov_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        double w = w0;
+        // four k-steps per trip: their eight loads go out together, ahead of the first MFMA (a wave waits
+        // on the panel, not on the matrix core); a step past the window adds 0 * 0 and changes nothing
+        for (int k0 = 0; k0 < rows; k0 += 4 * COV_KU) {
+            float fa[COV_KU], fb[COV_KU];
+#pragma unroll
+            for (int u = 0; u < COV_KU; ++u) {
+                const int k = k0 + 4 * u + kk;
+                const size_t off = (size_t)(k < rows ? hi - 1 - k : lo) * ldz;   // (lo: a row of the window, not used)
+                fa[u] = za[off];
+                fb[u] = zb[off];
+            }
+#pragma unroll
+            for (int u = 0; u < COV_KU; ++u) {
+#pragma clang fp contract(off)
+                const bool in = k0 + 4 * u + kk < rows;
+                const float pa = fa[u] * sa, pb = fb[u] * sb_;
+                const float ra = pa + ma, rb = pb + mb;
+                double a = (in && ina) ? (double)ra - ca_m : 0.0;
+                const double bb = (in && inb) ? (double)rb - cb_m : 0.0;
+                if (ew) { a = a * w; w = w * l4; }
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bb, acc, 0, 0, 0);
+            }
+        }
+        return acc;
+    };
+
+    double rho = 0.0, sc = 1.0, dg = 1e-6;   // Sigma = sc G + dg I
+    if (!ew) {
+        // pass 2: q_s = ||x_s||^2 per row (a wave per row, butterfly sum), then sum q and sum q^2
+        double t1 = 0.0, t2 = 0.0;
+        for (int s = lo + wv; s < hi; s += COV_WAVES) {
+            double q = 0.0;
+            for (int j = lane; j < N; j += 64) {
+                const double x = (double)ret(s, j) - ml[j];
+                q += x * x;
+            }
+            q = wave_sum(q);
+            t1 += q;
+            t2 += q * q;
+        }
+        // pass 3: ||G||_F^2 from the tiles, those off the diagonal twice; in a diagonal tile row < col twice
+        double fr = 0.0;
+        for (int q = wv; q < ntile; q += COV_WAVES) {
+            int I, J;
+            tile_of(q, I, J);
+            const cov_d4 acc = gram_tile(I, J);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = kk + 4 * r;
+                const double g2 = acc[r] * acc[r];
+                if (I != J || row < cl16) fr += 2.0 * g2;
+                else if (row == cl16) fr += g2;
+            }
+        }
+        fr = wave_sum(fr);
+        if (lane == 0) { red[wv] = t1; red[COV_WAVES + wv] = t2; red[2 * COV_WAVES + wv] = fr; }
+        __syncthreads();
+        double trG = 0.0, q4 = 0.0, fro = 0.0;
+        for (int w = 0; w < COV_WAVES; ++w) { trG += red[w]; q4 += red[COV_WAVES + w]; fro += red[2 * COV_WAVES + w]; }
+        if (rows > 0) {
+#pragma clang fp contract(off)
+            const double n = (double)rows, p = (double)N;
+            const double trS = trG / n, m = trS / p, delta_ = fro / (n * n);
+            if (estimator == KMPC_COV_LEDOIT_WOLF) {
+                double beta = (q4 / n - delta_) / (p * n);
+                const double delta = (delta_ - 2.0 * m * trS + p * (m * m)) / p;
+                beta = fmin(beta, delta);
+                rho = (beta == 0.0 || delta == 0.0) ? 0.0 : beta / delta;
+            } else {   // KMPC_COV_OAS
+                const double alpha = delta_ / (p * p);
+                const double num = alpha + m * m, den = (n + 1.0) * (alpha - (m * m) / p);
+                rho = den == 0.0 ? 1.0 : fmin(num / den, 1.0);
+            }
+            sc = (1.0 - rho) / n;
+            dg = rho * m + 1e-6;
+        } else {
+            rho = estimator == KMPC_COV_OAS ? 1.0 : 0.0;
+            sc = 0.0;
+        }
+    }
+    if (threadIdx.x == 0 && shrinkage) shrinkage[b] = rho;
+
+    // pass 4: the tiles again, scaled, stored with their mirror
+    double* out = sigma + (size_t)b * N * N;
+    double* tb = tbuf + wv * 16 * COV_TLD;
+    for (int q = wv; q < ntile; q += COV_WAVES) {
+        int I, J;
+        tile_of(q, I, J);
+        const cov_d4 acc = gram_tile(I, J);
+        if (I == J) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = kk + 4 * r, i = 16 * I + row, j = 16 * I + cl16;
+                if (row <= cl16 && j < N) {   // (i <= j < N)
+#pragma clang fp contract(off)
+                    double v = acc[r] * sc;
+                    if (i == j) v += dg;
+                    out[(size_t)i * N + j] = v;
+                    if (i != j) out[(size_t)j * N + i] = v;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma clang fp contract(off)
+                const int row = kk + 4 * r, i = 16 * I + row, j = 16 * J + cl16;   // (i < 16 J <= j: never the diagonal)
+                const double v = acc[r] * sc;
+                tb[row * COV_TLD + cl16] = v;
+                if (i < N && j < N) out[(size_t)i * N + j] = v;
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // the mirror: Sigma[16 J + c][16 I + lane & 15] = tile[lane & 15][c]
+                const int c = kk + 4 * r, i = 16 * I + cl16, j = 16 * J + c;
+                if (i < N && j < N) out[(size_t)j * N + i] = tb[cl16 * COV_TLD + c];
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
 }  // namespace
 
 // LDS of the small arrays (vec, Sm, pv, nu, dnu, rpv, red, flag, idg) and, for the LDS variant, M and Y
@@ -1136,6 +1353,22 @@ int rolling_moments_launch(int B, int T, int N, int lookback, const float* z, in
                            const float* stdv, const int* ts, double* mu, double* sigma, int* valid,
                            hipStream_t stream) {
     return rolling_moments_paths_launch(1, B, T, N, lookback, z, ldz, mean, stdv, ts, mu, sigma, valid, stream);
+}
+
+// kmpc_rolling_cov (P = 1) / kmpc_rolling_cov_paths: the arguments are checked by the C ABI. The sample
+// estimator IS rolling_moments_kernel (its bits are pinned), with the shrinkage zeroed on the stream.
+int rolling_cov_paths_launch(int P, int n_ts, int T, int N, int lookback, const float* z, int ldz,
+                             const float* mean, const float* stdv, const int* ts, double* mu, double* sigma,
+                             int* valid, int estimator, double lambda, double* shrinkage, hipStream_t stream) {
+    if (estimator == KMPC_COV_SAMPLE) {
+        if (shrinkage && hipMemsetAsync(shrinkage, 0, sizeof(double) * (size_t)n_ts * P, stream) != hipSuccess)
+            return KMPC_ERR_LAUNCH;
+        return rolling_moments_paths_launch(P, n_ts, T, N, lookback, z, ldz, mean, stdv, ts, mu, sigma, valid, stream);
+    }
+    hipLaunchKernelGGL(rolling_cov_kernel, dim3((unsigned)(n_ts * P)), dim3(COV_THREADS),
+                       sizeof(double) * cov_lds_doubles(N), stream, P, T, N, lookback, z, ldz, mean, stdv, ts, mu,
+                       sigma, valid, estimator, lambda, shrinkage);
+    return hipGetLastError() == hipSuccess ? KMPC_OK : KMPC_ERR_LAUNCH;
 }
 
 }  // namespace kmpc
