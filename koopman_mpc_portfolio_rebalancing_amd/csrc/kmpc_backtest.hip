@@ -49,9 +49,10 @@ __global__ void bt_metrics_kernel(int P, int S, const double* hist, double* m) {
         const double r = h[k * 4 + 1];
         var += (r - mean) * (r - mean);
         cum *= (1.0 + r);
-        peak = (k == 0) ? cum : fmax(peak, cum);   // np.maximum.accumulate(cumprod(1 + r))
+        // np.maximum.accumulate(cumprod(1 + r)) and np.min: a NaN stays (fmax / fmin alone drop it)
+        peak = (k == 0) ? cum : (cum != cum || peak != peak) ? cum + peak : fmax(peak, cum);
         const double dd = (cum - peak) / peak;
-        mdd = (k == 0) ? dd : fmin(mdd, dd);
+        mdd = (k == 0) ? dd : (dd != dd || mdd != mdd) ? dd + mdd : fmin(mdd, dd);
     }
     const double sd = sqrt(var / S);
     o[0] = sqrt(252.0) * mean / (sd + 1e-8);
